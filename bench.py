@@ -1,7 +1,16 @@
 """Benchmark of the MI355X USER-SPH engine on BASELINE.json's headline workload.
 
     python bench.py [--gpus N] [--scaling strong|weak] [--steps K] [--warmup W] [--edge 100]
-                    [--no-cpu] [--workload c2|c3|c5|c2pair|c5pair]
+                    [--workload c2|c3|c5|c2pair|c5pair] [--dump-outputs DIR]
+                    [--full [--no-cpu]]
+
+A plain run sets up, warms up, times the K steps, writes its outputs where --dump-outputs
+asks for them, and prints the result line.  --full adds what takes work of its own: the
+per-class kernel times of further steps, the CPU baselines (--no-cpu leaves those out)
+and c2pair's LAMMPS calling patterns.
+--dump-outputs DIR writes the arrays the timed path's caller holds after the last timed
+step as DIR/<name>.npy (float64, atoms in tag order; above 60 MB in all a fixed seeded
+sample of the atoms); the inputs are seeded, so two builds can be compared file by file.
 
 Workload (BASELINE.json configs[1]): 1M particles on a jittered 100^3 cubic lattice,
 periodic, hybrid/overlay sph/rhosum (nstep 1, h 3) + sph/taitwater (rho0 1, c0 10,
@@ -18,8 +27,9 @@ torch.distributed.run WORLD_SIZE must equal --gpus.
   --scaling weak: every brick holds an edge^3 share of a box edge*procgrid per side
       (N = 8 is BASELINE config C4: 200^3 = 8M particles on 2x2x2 GPUs).
 Rank 0 prints ONE JSON line.  `roofline` covers the dominant kernel (the taitwater force
-pass), timed live with HIP events recorded on the engine's stream; `cpu_baseline` is the
-reference's own compute code timed on this host on a bounded sample (rank 0, N = 1 only).
+pass), timed live with HIP events recorded on the engine's stream; `cpu_baseline` (--full)
+is the reference's own compute code timed on this host on a bounded sample (rank 0, N = 1
+only).
 """
 import argparse
 import importlib.util
@@ -43,6 +53,45 @@ def load_pkg():
     sys.modules["sph_amd"] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+def want_full(args):
+    return bool(getattr(args, "full", False))
+
+
+def want_cpu(args):
+    """The CPU baselines: part of --full, unless --no-cpu."""
+    return want_full(args) and not args.no_cpu
+
+
+DUMP_CAP_BYTES = 60 * 10 ** 6  # (under the 64 MB a dump may take in all)
+
+
+def dump_outputs(args, arrays, tag=None, rank=0, world=1):
+    """--dump-outputs DIR: the per-atom arrays of `arrays` (equal first dimension) as
+    DIR/<name>.npy in float64, rows in tag order where tags are given.  Where they exceed
+    DUMP_CAP_BYTES in all, the same seeded sample of the rows for every array."""
+    out_dir = getattr(args, "dump_outputs", None)
+    if not out_dir:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    rows = np.arange(n) if tag is None else np.argsort(tag, kind="stable")
+    per_row = sum(8 * (a.size // max(n, 1)) for a in arrays.values())
+    keep = DUMP_CAP_BYTES // max(world, 1) // max(per_row, 1)
+    if n > keep:
+        rows = rows[np.sort(np.random.default_rng(20240607).choice(n, size=keep, replace=False))]
+    for name, a in arrays.items():
+        fn = name if world == 1 else f"{name}.rank{rank}"
+        np.save(os.path.join(out_dir, fn + ".npy"), np.asarray(a, dtype=np.float64)[rows])
+
+
+def dump_engine_atoms(args, eng, rank=0, world=1):
+    if not getattr(args, "dump_outputs", None):
+        return
+    g = eng.get_atoms()
+    tag = g.pop("tag")
+    dump_outputs(args, g, tag, rank, world)
 
 
 def make_system(n, seed):
@@ -432,10 +481,7 @@ def c3_main(args, sph):
     eng.sync()
     elapsed = time.perf_counter() - t0
     st = eng.stats()
-    eng.set_timing(True)  # the other classes over 10 more steps, outside the timed region
-    eng.run(10)
-    eng.sync()
-    st_x = eng.stats()
+    dump_engine_atoms(args, eng)
     nloc = st["nlocal"]
     n_half = st["nbr_full"] / max(nloc, 1) / 2.0
     # morris 104 + 4 N_h, heat 56 + 4 N_h (fused here into one pass)
@@ -467,13 +513,18 @@ def c3_main(args, sph):
                      "achieved": ach, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                      "frac": ach / PEAK_HBM_GBS, "traffic": None,
                      "bytes_per_particle": bytes_pass, "ms_per_launch": ms_pass},
-        "kernels": {"neighbor_build_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
-                    "integrate_ms_per_step": st_x["ms_integrate"] / 10,
-                    "comm_ms_per_step": st_x["ms_comm"] / 10,
-                    "timing_note": "fused pass: HIP events in the timed region; the rest: 10 "
-                                   "further steps with every class timed"},
     }
-    if not args.no_cpu:
+    if want_full(args):
+        eng.set_timing(True)  # the other classes over 10 more steps, outside the timed region
+        eng.run(10)
+        eng.sync()
+        st_x = eng.stats()
+        out["kernels"] = {"neighbor_build_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
+                          "integrate_ms_per_step": st_x["ms_integrate"] / 10,
+                          "comm_ms_per_step": st_x["ms_comm"] / 10,
+                          "timing_note": "fused pass: HIP events in the timed region; the "
+                                         "rest: 10 further steps with every class timed"}
+    if want_cpu(args):
         cb = c3_cpu_baseline(args.cpu_n)
         if cb is not None:
             out["cpu_baseline"] = cb
@@ -599,9 +650,10 @@ def c2_pair_main(args, sph):
         wall += w
         for k, val in ms.items():
             acc[k] = acc.get(k, 0.0) + val / args.steps
+    dump_outputs(args, {"rho": r, "f": f, "drho": drho, "de": de})
     nls = max(args.steps, every) // every * every   # whole rebuild periods
     pattern = {}
-    for dl in (False, True):
+    for dl in (False, True) if want_full(args) else ():
         if dl:
             ctx.host_arrays(N, x=xs, vest=vs, rho=rs, e=es, f=f, drho=drho, de=de)
             for k in range(2):   # (untimed: first-use allocations of the device-list buffers)
@@ -613,7 +665,6 @@ def c2_pair_main(args, sph):
             lw += w
             lk += km
         pattern[dl] = (lw, lk)
-    lw, lk = pattern[False]
     n_full, n_half = foff[-1] / N, hoff[-1] / N
     by = {"rhosum": 40 + 4 * n_half, "taitwater": 104 + 4 * n_half}
     by["taitwater_list_reused"] = by["taitwater"]
@@ -631,30 +682,7 @@ def c2_pair_main(args, sph):
                                "= 3.3; the taitwater call after a list upload includes the "
                                "reverse half-list build",
                    "n_full_per_particle": n_full, "n_half_per_particle": n_half,
-                   "wall_ms_per_step_incl_pcie": wall / args.steps * 1e3,
-                   "lammps_pattern": {
-                       "what": "per step: sph_hip_atoms + sph_hip_list_keyed(FULL) + rhosum, "
-                               "sph_hip_atoms_rho + sph_hip_list_keyed(HALF) + taitwater; lists "
-                               f"rebuilt every {every} steps (key = build)",
-                       "steps": nls,
-                       "wall_ms_per_step_incl_pcie": lw / nls * 1e3,
-                       "kernel_ms_per_step": lk / nls,
-                       "wall_over_kernel": lw * 1e3 / max(lk, 1e-12)},
-                   "lammps_pattern_device_lists": {
-                       "what": "the shim's device-list path: LAMMPS' arrays registered as "
-                               "mapped host memory (sph_hip_host_arrays), sph_hip_atoms at a "
-                               "rebuild else sph_hip_atoms_update, sph_hip_build_list FULL / "
-                               "HALF at each new key (no host list copy or upload), rho "
-                               "written and f / drho / de added in place by the device",
-                       "wall_ms_by_call": {
-                           kind: dict(zip(("atoms", "build_full", "rhosum", "atoms_rho",
-                                           "build_half", "taitwater"),
-                                          [round(v / c, 4) for v in tot]), steps=c)
-                           for kind, (c, tot) in dl_parts.items()},
-                       "steps": nls,
-                       "wall_ms_per_step_incl_pcie": pattern[True][0] / nls * 1e3,
-                       "kernel_ms_per_step": pattern[True][1] / nls,
-                       "wall_over_kernel": pattern[True][0] * 1e3 / max(pattern[True][1], 1e-12)}},
+                   "wall_ms_per_step_incl_pcie": wall / args.steps * 1e3},
         "roofline": {"bound": "hbm", "kernel": "taitwater (half list: forward + reverse "
                                                "gather)",
                      "achieved": kern["taitwater"]["achieved_GBs"], "peak": PEAK_HBM_GBS,
@@ -662,6 +690,31 @@ def c2_pair_main(args, sph):
                      "traffic": None},
         "kernels": kern,
     }
+    if want_full(args):
+        lw, lk = pattern[False]
+        out["config"]["lammps_pattern"] = {
+            "what": "per step: sph_hip_atoms + sph_hip_list_keyed(FULL) + rhosum, "
+                    "sph_hip_atoms_rho + sph_hip_list_keyed(HALF) + taitwater; lists "
+                    f"rebuilt every {every} steps (key = build)",
+            "steps": nls,
+            "wall_ms_per_step_incl_pcie": lw / nls * 1e3,
+            "kernel_ms_per_step": lk / nls,
+            "wall_over_kernel": lw * 1e3 / max(lk, 1e-12)}
+        out["config"]["lammps_pattern_device_lists"] = {
+            "what": "the shim's device-list path: LAMMPS' arrays registered as "
+                    "mapped host memory (sph_hip_host_arrays), sph_hip_atoms at a "
+                    "rebuild else sph_hip_atoms_update, sph_hip_build_list FULL / "
+                    "HALF at each new key (no host list copy or upload), rho "
+                    "written and f / drho / de added in place by the device",
+            "wall_ms_by_call": {
+                kind: dict(zip(("atoms", "build_full", "rhosum", "atoms_rho",
+                                "build_half", "taitwater"),
+                               [round(v / c, 4) for v in tot]), steps=c)
+                for kind, (c, tot) in dl_parts.items()},
+            "steps": nls,
+            "wall_ms_per_step_incl_pcie": pattern[True][0] / nls * 1e3,
+            "kernel_ms_per_step": pattern[True][1] / nls,
+            "wall_over_kernel": pattern[True][0] * 1e3 / max(pattern[True][1], 1e-12)}
     print(json.dumps(out), flush=True)
     ctx.close()
 
@@ -751,6 +804,7 @@ def c5_pair_main(args, sph):
         wall += w
         for k, v in ms.items():
             acc[k] = acc.get(k, 0.0) + v / args.steps
+    dump_outputs(args, {"rho": rho, "cg": cg, "f": f, "de": de})
     t_dev = sum(acc.values()) * 1e-3
     n_full = d["full_off"][-1] / N
     n_half = d["half_off"][-1] / N
@@ -775,7 +829,7 @@ def c5_pair_main(args, sph):
                      "frac": kern[dom]["achieved_GBs"] / PEAK_HBM_GBS, "traffic": None},
         "kernels": kern,
     }
-    if not args.no_cpu:
+    if want_cpu(args):
         out["cpu_baseline"] = c5_pair_cpu(d)
     print(json.dumps(out), flush=True)
     ctx.close()
@@ -943,10 +997,16 @@ def c5_main(args, sph, dist=None, rank=0, world=1, dev=0):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     st = eng.stats()
-    eng.set_timing(True)  # the other classes over 3 more steps, outside the timed region
-    eng.run(3)
-    eng.sync()
-    st_x = eng.stats()
+    if getattr(args, "dump_outputs", None):
+        g = eng.get_atoms()
+        g.update({k: a for k, a in eng.get_atoms_multiphase().items() if k != "ninserted"})
+        dump_outputs(args, g, g.pop("tag"), rank, world)
+    st_x = None
+    if want_full(args):
+        eng.set_timing(True)  # the other classes over 3 more steps, outside the timed region
+        eng.run(3)
+        eng.sync()
+        st_x = eng.stats()
     nloc = st["nlocal"]
     n_full = st["nbr_full"] / max(nloc, 1)
     n_half = n_full / 2.0
@@ -996,17 +1056,19 @@ def c5_main(args, sph, dist=None, rank=0, world=1, dev=0):
                      "fill, timed with the neighbour build)" if rho_fused else
                      "full-list passes (rhosum/multiphase + colorgradient)"):
                         {"ms_per_step": ms_full, "achieved_GBs": ach_full,
-                         "bytes_per_particle": b_full},
-                    "neighbor_build_and_phase_change_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
-                    "integrate_ms_per_step": st_x["ms_integrate"] / 3,
-                    "comm_ms_per_step": st_x["ms_comm"] / 3,
-                    "timing_note": "pair passes: HIP events in the timed region; neighbor "
-                                   "build / phase change, integrate, comm: 3 further steps "
-                                   "with every class timed"},
+                         "bytes_per_particle": b_full}},
     }
+    if st_x is not None:
+        out["kernels"].update({
+            "neighbor_build_and_phase_change_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
+            "integrate_ms_per_step": st_x["ms_integrate"] / 3,
+            "comm_ms_per_step": st_x["ms_comm"] / 3,
+            "timing_note": "pair passes: HIP events in the timed region; neighbor "
+                           "build / phase change, integrate, comm: 3 further steps "
+                           "with every class timed"})
     attach_pmc_traffic(out, "k_mp2_gather", b_half * nloc, world, args,
                        fname="pmc_traffic_c5.json")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and want_cpu(args):
         out["cpu_baseline"] = c5_cpu_baseline(args.c5_cpu_n, steps=1)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -1121,7 +1183,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--edge", type=int, default=None,
                     help="lattice edge (default 100; c5pair 80: C5's ~0.5M particles per GPU)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes work of its own: per-class kernel times of further "
+                         "steps, the CPU baselines, c2pair's LAMMPS calling patterns")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path leaves after its last timed step as "
+                         "DIR/<name>.npy (float64; a fixed seeded sample of the atoms above "
+                         "60 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: without the CPU baselines")
     ap.add_argument("--cpu-n", type=int, default=100)
     ap.add_argument("--c5-cpu-n", type=int, default=100,
                     help="c5: edge of the two-phase block the reference's five styles are "
@@ -1280,11 +1349,7 @@ def main():
     barrier()
     elapsed = max_over_ranks(t1 - t0)
     st = eng.stats()
-    # the other classes (rebuild, integrate, comm) over 10 more steps, outside the timed region
-    eng.set_timing(True)
-    eng.run(10)
-    eng.sync()
-    st_x = eng.stats()
+    dump_engine_atoms(args, eng, rank, world)
 
     nloc = st["nlocal"]
     total_ps = n_total * args.steps / elapsed
@@ -1315,15 +1380,23 @@ def main():
                       "rhosum+taitwater": {"achieved_GBs": ach_pair,
                                            "frac": ach_pair / PEAK_HBM_GBS,
                                            "kernel_particle_steps_per_s":
-                                               nloc / ((ms_tait + ms_rho) * 1e-3)},
-                      "neighbor_build_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
-                      "integrate_ms_per_step": st_x["ms_integrate"] / 10,
-                      "comm_ms_per_step": st_x["ms_comm"] / 10,
-                      "timing_note": "rhosum/taitwater: HIP events in the timed region; "
-                                     "neighbor build, integrate, comm: 10 further steps "
-                                     "with every class timed"}
+                                               nloc / ((ms_tait + ms_rho) * 1e-3)}}
+    if want_full(args):
+        # the other classes (rebuild, integrate, comm) over 10 more steps, outside the timed
+        # region
+        eng.set_timing(True)
+        eng.run(10)
+        eng.sync()
+        st_x = eng.stats()
+        out["kernels"].update({
+            "neighbor_build_ms": st_x["ms_neigh"] / max(st_x["n_neigh"], 1),
+            "integrate_ms_per_step": st_x["ms_integrate"] / 10,
+            "comm_ms_per_step": st_x["ms_comm"] / 10,
+            "timing_note": "rhosum/taitwater: HIP events in the timed region; "
+                           "neighbor build, integrate, comm: 10 further steps "
+                           "with every class timed"})
     attach_pmc_traffic(out, kname, bytes_tait * nloc, world, args)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and want_cpu(args):
         out["cpu_baseline"] = cpu_baseline(args.cpu_n)
         # beside it, the same reference code on all the cores this process may use (one
         # brick per process)

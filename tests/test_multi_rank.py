@@ -120,6 +120,31 @@ def test_strong_lattice_partition():
     assert np.array_equal(xs, x0) and np.array_equal(vs, v0)
 
 
+def test_dump_outputs_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 arrays in tag order; above the size cap one seeded sample of
+    the rows, the same for every array and from call to call."""
+    import argparse
+
+    import bench
+    n = 1000
+    tag = np.random.default_rng(1).permutation(n).astype(np.int32)
+    arrays = {"x": np.stack([tag, tag, tag], 1).astype(np.float64), "rho": tag.astype(np.float32)}
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "all"))
+    bench.dump_outputs(args, arrays, tag)
+    x, rho = np.load(tmp_path / "all" / "x.npy"), np.load(tmp_path / "all" / "rho.npy")
+    assert x.dtype == rho.dtype == np.float64
+    assert np.array_equal(rho, np.arange(n)) and np.array_equal(x[:, 2], rho)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 32 * 100)       # 32 B per row: 100 rows
+    for d in ("s1", "s2"):
+        bench.dump_outputs(argparse.Namespace(dump_outputs=str(tmp_path / d)), arrays, tag)
+    x1, r1 = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s1" / "rho.npy")
+    assert x1.shape == (100, 3) and r1.shape == (100,)
+    assert x1.nbytes + r1.nbytes <= 32 * 100
+    assert np.array_equal(x1[:, 0], r1) and (np.diff(r1) > 0).all()
+    assert np.array_equal(r1, np.load(tmp_path / "s2" / "rho.npy"))
+    bench.dump_outputs(argparse.Namespace(dump_outputs=None), arrays, tag)   # off: no-op
+
+
 def test_bench_rejects_world_mismatch():
     import subprocess
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
@@ -150,7 +175,8 @@ def test_bench_two_gpus(workload):
     ndev = int(probe.stdout.strip().splitlines()[-1]) if probe.returncode == 0 else 0
     if ndev < 2:
         pytest.skip(f"{ndev} HIP device(s) visible")
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu", "--workload", workload]
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu",
+            "--workload", workload]
     if workload == "c5":
         args += ["--edge", "60"]
     out = _bench_json(args)
@@ -165,6 +191,7 @@ def test_bench_two_processes_ipc(workload, edge):
     hipIpc halos between the two processes, barrier + max-over-ranks timing, ONE JSON line
     from rank 0 -- the multi-GPU bench path with only the byte mover swapped."""
     out = _bench_json(["--gpus", "2", "--transport", "ipc", "--steps", "3", "--warmup", "1",
-                       "--no-cpu", "--workload", workload, "--edge", edge])
+                       "--full", "--no-cpu", "--workload", workload, "--edge", edge])
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert "hipIpc" in out["config"]["parallelism"]
+    assert out["kernels"]["integrate_ms_per_step"] > 0   # (--full: the further steps' times)

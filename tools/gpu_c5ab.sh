@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest tests/test_c5_engine.py tests/test_c5_bric
   --timeout 240 --timeout-method thread > gpurun_out/c5ab/tests.log 2>&1 || { tail -30 gpurun_out/c5ab/tests.log; exit 1; }
 tail -2 gpurun_out/c5ab/tests.log
 fi
-ARGS=${AB_ARGS:---workload c5 --steps 10 --warmup 3 --no-cpu}
+ARGS=${AB_ARGS:---full --workload c5 --steps 10 --warmup 3 --no-cpu}
 for SPEC in "$@"; do
   IFS=: read -r L ENVS <<< "$SPEC"
   P=lammps-sph-multiphase_amd/$L; [ "$L" = prod ] && P=lammps-sph-multiphase_amd/libsph_hip.so

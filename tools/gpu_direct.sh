@@ -9,5 +9,5 @@ tail -2 gpurun_out/tb.log
 [ $rc -eq 0 ] || { grep -m8 -E "FAILED|Error|error" gpurun_out/tb.log; exit $rc; }
 for d in 0 1; do for e in 50 100; do
   echo -n "direct $d edge $e loopback: "
-  SPH_DIRECT=$d timeout -k 10 200 python3 bench.py --edge $e --comm-loopback --steps 100 --warmup 20 --no-cpu 2>/dev/null | python3 -c "import json,sys;d=json.load(sys.stdin);print(round(d['ms_per_step'],4), 'ms/step comm', round(d['kernels']['comm_ms_per_step'],4), 'rebuild', round(d['kernels']['neighbor_build_ms'],3))" || exit 1
+  SPH_DIRECT=$d timeout -k 10 200 python3 bench.py --full --edge $e --comm-loopback --steps 100 --warmup 20 --no-cpu 2>/dev/null | python3 -c "import json,sys;d=json.load(sys.stdin);print(round(d['ms_per_step'],4), 'ms/step comm', round(d['kernels']['comm_ms_per_step'],4), 'rebuild', round(d['kernels']['neighbor_build_ms'],3))" || exit 1
 done; done

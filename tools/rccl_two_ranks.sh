@@ -4,4 +4,4 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R"
 timeout -k 10 150 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --edge 24 --steps 10 --warmup 2
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --edge 24 --steps 10 --warmup 2
