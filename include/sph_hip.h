@@ -396,6 +396,74 @@ int sph_engine_phase_change(sph_engine *e, const sph_phasechange_params *p, int 
    sortfreq steps (0 = never).  Default 1000 / 0, LAMMPS' own.  The engine's rows keep their
    own order; only the tracked LAMMPS order changes. */
 int sph_engine_atom_sort(sph_engine *e, int sortfreq, double binsize);
+
+/* Static regions (box units), shared by the clamps and the reductions below.  The
+   predicates are LAMMPS' own, closed boundaries included: sphere
+   sqrt(dx*dx+dy*dy+dz*dz) <= radius (region_sphere.cpp:96-105), block x >= xlo && x <= xhi
+   && ... (region_block.cpp:114-119), match = !(inside ^ interior) (region.cpp:127-131).
+   Moving and variable-shape regions cannot be expressed. */
+#define SPH_REGION_SPHERE 0
+#define SPH_REGION_BLOCK 1
+typedef struct {
+  int style;                           /* SPH_REGION_* */
+  int interior;                        /* 1 = side in (LAMMPS' default), 0 = side out */
+  double xc, yc, zc, radius;           /* sphere */
+  double xlo, xhi, ylo, yhi, zlo, zhi; /* block */
+} sph_region;
+
+/* fix setmeso / fix setmesode, constant style (FixSetMeso::post_force,
+   fix_setmeso.cpp:180-233; FixSetMesodE::post_force, fix_setmesode.cpp:171-198): the named
+   field of every owned atom of the group (type_mask) that the region selects at its current
+   position is overwritten.  Up to SPH_MAX_SETMESO fixes, applied in call order by one
+   kernel where LAMMPS runs post_force: at the end of setup and in every step after the
+   whole pair compute, before that step's final integrate.  Created and migrated atoms are
+   clamped from the step they are owned.  Single-phase and multiphase engines; on a
+   single-phase engine SPH_SET_T needs one cv for all atoms (set_atoms' cv, default 1),
+   checked at setup.  Before sph_engine_setup.  SPH_HIP_EINVAL: unknown `what` or region
+   style, negative radius, after setup, too many fixes, SPH_SET_DE with region_mode 2
+   (setmesode has no noregion). */
+#define SPH_MAX_SETMESO 8
+#define SPH_SET_RHO 0   /* fix setmeso meso_rho : rho = value */
+#define SPH_SET_E 1     /* fix setmeso meso_e   : e   = value */
+#define SPH_SET_T 2     /* fix setmeso meso_t   : e   = cv * value (sph_t2energy) */
+#define SPH_SET_DE 3    /* fix setmesode        : de  = value */
+typedef struct {
+  int what;            /* SPH_SET_* */
+  double value;
+  int type_mask;       /* bit t: type t is in the fix's group; 0 = all */
+  int region_mode;     /* 0 none, 1 `region` (where match), 2 `noregion` (where !match) */
+  sph_region region;
+} sph_setmeso;
+int sph_engine_setmeso(sph_engine *e, const sph_setmeso *fix);
+
+/* Group reductions on the device (the thermo output of bubble.lmp:77-90 without a
+   get_atoms round trip): for each of nsel <= SPH_MAX_REDUCE selections, sum / min / max of
+   one per-atom quantity and the atom count over the owned atoms of this rank that the
+   group and region select, in the state sph_engine_get_atoms would return; all selections
+   in one pass.  An empty selection gives count 0, sum 0, min +inf, max -inf; the average is
+   sum / count; combining ranks is the caller's (as the computes' Allreduce).  Fixed-shape
+   reduction without atomics: two calls on the same state return identical bits.  After
+   setup.  On a single-phase engine SPH_Q_T needs one cv for all atoms. */
+#define SPH_MAX_REDUCE 16
+#define SPH_Q_ONE 0     /* 1 per atom */
+#define SPH_Q_RHO 1
+#define SPH_Q_E 2
+#define SPH_Q_T 3       /* e / cv */
+#define SPH_Q_DE 4
+#define SPH_Q_MASS 5    /* rmass, or mass[type] */
+#define SPH_Q_KE 6      /* 0.5 m |v|^2 */
+typedef struct {
+  int quantity;        /* SPH_Q_* */
+  int type_mask;
+  int region_mode;
+  sph_region region;
+} sph_reduce_sel;
+typedef struct {
+  double sum, min, max;
+  int64_t count;
+} sph_reduce_out;
+int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_reduce_out *out);
+
 /* Multiphase fields of the owned atoms in get_atoms order (any pointer may be NULL):
    rmass, cv, colorgradient (n*3), vest (n*3), type; *ninserted = atoms created so far. */
 int sph_engine_get_atoms_multiphase(sph_engine *e, double *rmass, double *cv, double *cg,

@@ -97,8 +97,90 @@ class EngineStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+SPH_REGION_SPHERE, SPH_REGION_BLOCK = 0, 1
+SPH_SET_RHO, SPH_SET_E, SPH_SET_T, SPH_SET_DE = 0, 1, 2, 3
+SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7)
+SPH_MAX_SETMESO, SPH_MAX_REDUCE = 8, 16
+SET_FIELDS = {"rho": SPH_SET_RHO, "e": SPH_SET_E, "t": SPH_SET_T, "de": SPH_SET_DE}
+QUANTITIES = {"one": SPH_Q_ONE, "rho": SPH_Q_RHO, "e": SPH_Q_E, "t": SPH_Q_T, "de": SPH_Q_DE,
+              "mass": SPH_Q_MASS, "ke": SPH_Q_KE}
+
+
+class Region(C.Structure):
+    """sph_region (include/sph_hip.h section 2): a static sphere or block, box units."""
+    _fields_ = [("style", C.c_int), ("interior", C.c_int),
+                ("xc", C.c_double), ("yc", C.c_double), ("zc", C.c_double),
+                ("radius", C.c_double),
+                ("xlo", C.c_double), ("xhi", C.c_double), ("ylo", C.c_double),
+                ("yhi", C.c_double), ("zlo", C.c_double), ("zhi", C.c_double)]
+
+
+class SetMeso(C.Structure):
+    """sph_setmeso: one fix setmeso / setmesode of constant style."""
+    _fields_ = [("what", C.c_int), ("value", C.c_double), ("type_mask", C.c_int),
+                ("region_mode", C.c_int), ("region", Region)]
+
+
+class ReduceSel(C.Structure):
+    """sph_reduce_sel: one quantity over a group and region."""
+    _fields_ = [("quantity", C.c_int), ("type_mask", C.c_int), ("region_mode", C.c_int),
+                ("region", Region)]
+
+
+class ReduceOut(C.Structure):
+    """sph_reduce_out"""
+    _fields_ = [("sum", C.c_double), ("min", C.c_double), ("max", C.c_double),
+                ("count", C.c_int64)]
+
+
+def _side(side):
+    if side not in ("in", "out"):
+        raise ValueError(f"side must be 'in' or 'out', not {side!r}")
+    return 1 if side == "in" else 0
+
+
+def sphere(center, radius, side="in") -> Region:
+    """region sphere xc yc zc radius side in|out"""
+    r = Region()
+    r.style, r.interior = SPH_REGION_SPHERE, _side(side)
+    r.xc, r.yc, r.zc = (float(c) for c in center)
+    r.radius = float(radius)
+    return r
+
+
+def block(lo, hi, side="in") -> Region:
+    """region block xlo xhi ylo yhi zlo zhi side in|out"""
+    r = Region()
+    r.style, r.interior = SPH_REGION_BLOCK, _side(side)
+    r.xlo, r.ylo, r.zlo = (float(c) for c in lo)
+    r.xhi, r.yhi, r.zhi = (float(c) for c in hi)
+    return r
+
+
+def _type_mask(types):
+    """None = every type (mask 0), else the bits of the listed types"""
+    if types is None:
+        return 0
+    m = 0
+    for t in ([types] if np.isscalar(types) else types):
+        m |= 1 << int(t)
+    return m
+
+
+def _region_mode(region, noregion):
+    if region is not None and noregion is not None:
+        raise ValueError("give region or noregion, not both")
+    if region is not None:
+        return 1, region
+    if noregion is not None:
+        return 2, noregion
+    return 0, Region()
+
+
 EXPORTS = {
     # name: (restype, argtypes)
+    "sph_engine_setmeso": (_i, [_vp, C.POINTER(SetMeso)]),
+    "sph_engine_reduce": (_i, [_vp, _i, _vp, _vp]),
     "sph_hip_last_error": (C.c_char_p, []),
     "sph_hip_abi_version": (_i, []),
     "sph_hip_device_count": (_i, []),
@@ -584,6 +666,33 @@ class Engine:
         """atom_modify sort sortfreq binsize: the LAMMPS local order fix phase_change meets its
         candidates in (Atom::sort at setup and every sortfreq steps; 0 = never)."""
         _chk(self.L.sph_engine_atom_sort(self.h, int(sortfreq), float(binsize)))
+
+    def setmeso(self, what, value, types=None, region=None, noregion=None):
+        """fix setmeso meso_rho|meso_e|meso_t value [region|noregion R] / fix setmesode value
+        [region R] on the group of `types` (None = all): what = "rho" | "e" | "t" | "de" or
+        SPH_SET_*; region / noregion = sphere(...) | block(...).  Before setup()."""
+        f = SetMeso()
+        f.what = SET_FIELDS[what] if isinstance(what, str) else int(what)
+        f.value = float(value)
+        f.type_mask = _type_mask(types)
+        f.region_mode, f.region = _region_mode(region, noregion)
+        _chk(self.L.sph_engine_setmeso(self.h, C.byref(f)))
+
+    def reduce(self, selections):
+        """sph_engine_reduce: selections = dicts(quantity="one"|"rho"|"e"|"t"|"de"|"mass"|"ke"
+        or SPH_Q_*, types=None, region=None, noregion=None), at most SPH_MAX_REDUCE, evaluated
+        in one pass over the owned atoms -> [dict(sum, min, max, count)]."""
+        n = len(selections)
+        sel = (ReduceSel * max(n, 1))()
+        for k, d in enumerate(selections):
+            q = d["quantity"]
+            sel[k].quantity = QUANTITIES[q] if isinstance(q, str) else int(q)
+            sel[k].type_mask = _type_mask(d.get("types"))
+            sel[k].region_mode, sel[k].region = _region_mode(d.get("region"), d.get("noregion"))
+        out = (ReduceOut * max(n, 1))()
+        _chk(self.L.sph_engine_reduce(self.h, n, C.cast(sel, C.c_void_p),
+                                      C.cast(out, C.c_void_p)))
+        return [dict(sum=o.sum, min=o.min, max=o.max, count=int(o.count)) for o in out[:n]]
 
     def get_atoms_multiphase(self):
         n = self.nlocal

@@ -26,6 +26,7 @@
 #endif
 #include "sph_engine_kernels.h"
 #include "sph_engine_mp.h"
+#include "sph_fix_kernels.h"
 #include "sph_ipc.h"
 #include "sph_mp2_kernels.h"
 #include "sph_pc.h"
@@ -230,6 +231,13 @@ struct sph_engine {
   int pc_nevery = 1, pc_seed = 0;
   int64_t pc_next = 1, pc_inserted = 0;
   int tag_next = 0;  // tag of the next created atom (atom->tag_extend)
+  // fix setmeso / setmesode clamps (sph_engine_setmeso), applied in call order by k_setmeso
+  // after every pair compute of setup() and run() -- LAMMPS' post_force
+  SetMesoArgs sm{};
+  bool sm_needs_cv = false;  // a SPH_SET_T clamp is armed
+  // sph_engine_reduce: the blocks' partials and the folded results
+  DBuf<ReducePart> red_part;
+  DBuf<sph_reduce_out> red_out;
   bool pc_tags_agreed = false;  // bricks: tag_next agreed over the ranks (first call)
   std::vector<double> cv_by_tag;  // single-phase engines: the constant cv, for restarts
 
@@ -2510,6 +2518,30 @@ struct sph_engine {
     pc_inserted += nins;
   }
 
+  // single-phase engines keep no per-atom cv on the device (atom_style meso's cv takes no
+  // part in its pair styles): meso_t clamps and temperature reductions take the one cv all
+  // atoms were set with
+  double uniform_cv(const char *who) const {
+    double c = cv_by_tag.empty() ? 1.0 : cv_by_tag[0];
+    for (double v : cv_by_tag)
+      SPH_REQUIRE(v == c, SPH_HIP_EINVAL,
+                  "%s on a single-phase engine needs one cv for all atoms (got %g and %g); "
+                  "per-atom cv is the multiphase engine's",
+                  who, c, v);
+    return c;
+  }
+
+  // FixSetMeso / FixSetMesodE post_force of the armed clamps on the owned rows: one launch,
+  // none without a clamp
+  void post_force_setmeso() {
+    if (sm.nfix == 0 || nlocal == 0) return;
+    Scope t(this, T_INT);
+    const double cvc = (!mp && sm_needs_cv) ? uniform_cv("fix setmeso meso_t") : 1.0;
+    hipLaunchKernelGGL(k_setmeso, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, sm, xf.p, vr.p,
+                       en.p, de.p, ty.p, mp ? (const double *)cvv.p : nullptr, cvc,
+                       (!mp && (force_mode & M_TAIT)) ? (const Coefs *)dc : nullptr);
+  }
+
   bool rhosum_due() const {
     return cfg.rhosum_nstep > 0 && (step % cfg.rhosum_nstep) == 0;
   }
@@ -2532,6 +2564,7 @@ struct sph_engine {
     hipLaunchKernelGGL(k_vest_from_v, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal,
                        cfg.stationary_mask, ty.p, vel.p, vr.p);
     pair_compute(rhosum_due(), /*setup=*/true);
+    post_force_setmeso();  // (FixSetMeso::setup calls post_force)
     last_build = 0;
     setup_done = true;
   }
@@ -2568,6 +2601,7 @@ struct sph_engine {
         forward();
         pair_compute(rhosum_due());
       }
+      post_force_setmeso();
       refresh_inner(!pc && (step + 1 - last_build) % every == 0);
       if (timing && pending.size() > 4096) harvest();
     }
@@ -2788,6 +2822,8 @@ int sph_engine_destroy(sph_engine *e) {
   e->pc_k0.release();
   e->pc_k1.release();
   e->pc_cnt.release();
+  e->red_part.release();
+  e->red_out.release();
   for (auto *b : {&e->ty, &e->ty2, &e->tag, &e->tag2, &e->gowner, &e->gimg, &e->sel, &e->nsel,
                   &e->bidx, &e->bidx2, &e->cnt, &e->off, &e->nbr, &e->mx,
                   &e->ccnt, &e->pcnt, &e->qbeg, &e->tb, &e->xpos, &e->sel2, &e->rows_in, &e->rows_bd, &e->tnbr,
@@ -2930,6 +2966,75 @@ int sph_engine_phase_change(sph_engine *e, const sph_phasechange_params *p, int 
   e->pc_nevery = nevery;
   e->pc_seed = seed;
   e->pc_next = e->step + 1;  // next_reneighbor = ntimestep + 1 (fix_phase_change.cpp:120)
+  SPH_API_END
+}
+
+static void check_region(const char *who, int region_mode, const sph_region &r) {
+  SPH_REQUIRE(region_mode >= 0 && region_mode <= 2, SPH_HIP_EINVAL, "%s: region_mode %d", who,
+              region_mode);
+  if (region_mode == 0) return;
+  SPH_REQUIRE(r.style == SPH_REGION_SPHERE || r.style == SPH_REGION_BLOCK, SPH_HIP_EINVAL,
+              "%s: unknown region style %d", who, r.style);
+  if (r.style == SPH_REGION_SPHERE)  // "Illegal region sphere command" (region_sphere.cpp:70)
+    SPH_REQUIRE(r.radius >= 0.0, SPH_HIP_EINVAL, "%s: sphere radius %g < 0", who, r.radius);
+}
+
+int sph_engine_setmeso(sph_engine *e, const sph_setmeso *fix) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && fix, SPH_HIP_EINVAL, "sph_engine_setmeso: NULL argument");
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_setmeso: arm the fix before sph_engine_setup");
+  SPH_REQUIRE(fix->what >= SPH_SET_RHO && fix->what <= SPH_SET_DE, SPH_HIP_EINVAL,
+              "sph_engine_setmeso: unknown field %d", fix->what);
+  check_region("sph_engine_setmeso", fix->region_mode, fix->region);
+  SPH_REQUIRE(!(fix->what == SPH_SET_DE && fix->region_mode == 2), SPH_HIP_EINVAL,
+              "sph_engine_setmeso: fix setmesode has no noregion");
+  SPH_REQUIRE(e->sm.nfix < SPH_MAX_SETMESO, SPH_HIP_EINVAL,
+              "sph_engine_setmeso: more than %d fixes", SPH_MAX_SETMESO);
+  e->sm.fix[e->sm.nfix++] = *fix;
+  if (fix->what == SPH_SET_T) e->sm_needs_cv = true;
+  SPH_API_END
+}
+
+int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_reduce_out *out) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && nsel >= 0 && (nsel == 0 || (sel && out)), SPH_HIP_EINVAL,
+              "sph_engine_reduce: bad argument");
+  SPH_REQUIRE(nsel <= SPH_MAX_REDUCE, SPH_HIP_EINVAL,
+              "sph_engine_reduce: %d selections > %d", nsel, SPH_MAX_REDUCE);
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "sph_engine_reduce: call sph_engine_setup first");
+  ReduceArgs a{};
+  a.nsel = nsel;
+  bool needs_cv = false;
+  for (int k = 0; k < nsel; k++) {
+    SPH_REQUIRE(sel[k].quantity >= SPH_Q_ONE && sel[k].quantity <= SPH_Q_KE, SPH_HIP_EINVAL,
+                "sph_engine_reduce: selection %d: unknown quantity %d", k, sel[k].quantity);
+    check_region("sph_engine_reduce", sel[k].region_mode, sel[k].region);
+    a.sel[k] = sel[k];
+    needs_cv = needs_cv || sel[k].quantity == SPH_Q_T;
+  }
+  if (nsel == 0) return SPH_HIP_OK;
+  const double cvc = (!e->mp && needs_cv) ? e->uniform_cv("SPH_Q_T") : 1.0;
+  const int n = e->nlocal;
+  if (n == 0) {
+    for (int k = 0; k < nsel; k++) out[k] = sph_reduce_out{0.0, HUGE_VAL, -HUGE_VAL, 0};
+    return SPH_HIP_OK;
+  }
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  const int nb = (int)std::min<long>(blocks(n), RED_MAXBLOCKS);
+  e->red_part.reserve((size_t)RED_MAXBLOCKS * SPH_MAX_REDUCE);
+  e->red_out.reserve(SPH_MAX_REDUCE);
+  StepMass sm;
+  for (int t = 0; t <= MAXT; t++) sm.mass[t] = e->sc.mass[t];
+  hipLaunchKernelGGL(k_reduce_part, dim3(nb), dim3(RED_THREADS), 0, e->s, n, a, e->xf.p, e->vr.p,
+                     e->en.p, e->de.p, e->ty.p, e->vel.p, e->mp ? (const double *)e->rm.p : nullptr,
+                     e->mp ? (const double *)e->cvv.p : nullptr, cvc, sm, e->red_part.p);
+  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(64), 0, e->s, nb, nsel, e->red_part.p,
+                     e->red_out.p);
+  SPH_HIP_TRY(hipGetLastError());
+  SPH_HIP_TRY(hipMemcpyAsync(out, e->red_out.p, nsel * sizeof(sph_reduce_out),
+                             hipMemcpyDeviceToHost, e->s));
+  SPH_HIP_TRY(hipStreamSynchronize(e->s));
   SPH_API_END
 }
 
