@@ -101,14 +101,6 @@ constexpr int BLK_CH = 1024, BLK_CHE = 1280;
 // the force pass's VISC for one type with Monaghan viscosity and viscC = 0 (no viscosity
 // term; the engine selects it, sph_engine.hip force_pass)
 constexpr int BLK_VISC_NONE = 2;
-// Newton-3 inside the blocks (k_blk_build N3 + the passes' LDS share accumulators): measured
-// slower on gfx950 (force 0.291 -> 0.313 ms, build 1.60 -> 2.18 ms at C2 1M),
-// so only study builds carry it (SPH_N3=1)
-#ifdef SPH_STUDY
-constexpr bool BLK_N3_BUILT = true;
-#else
-constexpr bool BLK_N3_BUILT = false;
-#endif
 __host__ __device__ inline int blk_q(int s, int cq) { return (s >> 4) * cq + (s & 15); }
 template <int CQ>
 __device__ __forceinline__ int blk_s(int q) { return (q / CQ) * 16 + (q % CQ); }
@@ -461,13 +453,7 @@ __device__ __forceinline__ unsigned long long blk_uniform64(unsigned long long x
 // BEXP (study builds, SPH_BEXP with the build v2): 1 = return after the bin table, 2 = after
 // the candidates, 3 = no emit (rows not written), 4 = no tests (every word 0).  Outputs
 // meaningless.
-// N3 (Newton's third law inside the block): the union puts the block's own rows first
-// (slot r + 1 = row r, whether or not a list names it), and a row keeps a neighbour that is
-// another row of the block only if that row comes after it -- each such pair is evaluated
-// once, by its earlier row, which also accumulates the later row's share (the pair passes'
-// LDS accumulators).  rcnt/icnt then hold the rows' stored (N3) counts and fcnt the full
-// counts (Neighbor::full_bin's, for the neighbour statistics).
-template <int R, int G, int U, bool NT1, bool INNER, bool N3, int BEXP = 0, int SC = BLK_SCAP>
+template <int R, int G, int U, bool NT1, bool INNER, int BEXP = 0, int SC = BLK_SCAP>
 __global__ void __launch_bounds__(256)
 k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
             const int *__restrict__ ty, const double4 *__restrict__ xb,
@@ -475,15 +461,14 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
             const Coefs *__restrict__ cf, int ucap, int sstride, int *__restrict__ ulist,
             int *__restrict__ ucnt, int *__restrict__ rcnt, unsigned short *__restrict__ snbr,
             int *__restrict__ icnt, unsigned short *__restrict__ snbi,
-            int *__restrict__ ovf, int *__restrict__ umax, int cq, int *__restrict__ fcnt,
-            unsigned char *__restrict__ bperm, int *__restrict__ uilist,
+            int *__restrict__ ovf, int *__restrict__ umax, int cq, int *__restrict__ uilist,
             int *__restrict__ uicnt, int *__restrict__ kcnt) {
   constexpr int NT = 256, NW = NT / 64, MCH = BLK_MCAP / 64, SCH = SC / 64;
   constexpr int RPW = R / NW, UG = U * G, WS = INNER ? 2 : 1;
   // the INNER UNION (uilist != nullptr): the inner rows index a union of their own -- the
   // atoms some inner row names, ~15 % fewer than the full union at C2 -- so the passes stage
   // a smaller LDS image while the inner rows are live (more workgroups per CU)
-  const bool iu = INNER && !N3 && uilist != nullptr;
+  const bool iu = INNER && uilist != nullptr;
   static_assert(R <= 64 && R % 32 == 0, "one lane per row, rows in steps of 8 per wave");
   static_assert(UG <= 64, "a row's padding in one store");
   // the rows' hit words per chunk (full, inner); before the tests the same storage holds
@@ -502,12 +487,9 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
   __shared__ double4 s_row[R];
   __shared__ int s_rty[R];
   __shared__ int s_self[NW][64];
-  __shared__ unsigned long long s_rowm[N3 ? SCH : 1];  // N3: kept candidates that are rows
-  __shared__ int s_fc[N3 ? R : 1];                      // N3: the rows' full counts
   __shared__ double s_bb[6];
   __shared__ double s_cns[NT1 ? 1 : NT2], s_cin[(NT1 || !INNER) ? 1 : NT2];
   __shared__ int s_sc[NW];
-  __shared__ int s_len[R];  // (bperm: the rows' walked lengths)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, 
             wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform: scalar)
   const int row0 = b * R;
@@ -518,7 +500,6 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
       s_cns[t] = cf->cutneighsq[t];
       if (INNER) s_cin[t] = cf->cutinsq[t];
     }
-  if (N3 && tid < R) s_fc[tid] = 0;
   // 1) the rows (far away past the last row: never a hit) and their bounding box (wave 0)
   if (wv == 0) {
     double lo[3], hi[3];
@@ -658,7 +639,6 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
   };
   double4 xn;
   int tn = 1;
-  int fc = 0;  // N3: lane r's share of row r's full count
   if (wv < nch) cload(wv, xn, tn);
   for (int c = wv; c < nch; c += NW) {
     const int p = c * 64 + lane;
@@ -699,21 +679,8 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
     // (rows past the last one sit at 1e300: their words are 0 already)
     const int self = s_self[wv][lane];
     const unsigned long long sbit = (unsigned long long)(self >= 0) << (self & 63);
-    unsigned long long keep = ~sbit;
-    if (N3) {  // lane r also drops the rows before it: prefix OR of the rows' own bits
-      unsigned long long lo = sbit;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned a = (unsigned)__shfl_up((int)(unsigned)lo, d, 64);
-        const unsigned h = (unsigned)__shfl_up((int)(unsigned)(lo >> 32), d, 64);
-        if (lane >= d) lo |= ((unsigned long long)h << 32) | a;
-      }
-      keep = ~lo;
-    }
-    const unsigned long long full = (((unsigned long long)my_hi << 32) | my_lo) & ~sbit;
-    const unsigned long long mine = full & keep;
-    const unsigned long long minei = (((unsigned long long)mi_hi << 32) | mi_lo) & keep;
-    if (N3 && lane < R) fc += __popcll(full);
+    const unsigned long long mine = (((unsigned long long)my_hi << 32) | my_lo) & ~sbit;
+    const unsigned long long minei = (((unsigned long long)mi_hi << 32) | mi_lo) & ~sbit;
     if (lane < R) {
       if (INNER)
         reinterpret_cast<ulonglong2 *>(s_w)[c * R + lane] = make_ulonglong2(mine, minei);
@@ -729,26 +696,16 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
       for (int d = 32; d > 0; d >>= 1) ui |= __shfl_xor(ui, d, 64);
       if (lane == 0) s_usedi[c] = ui;
     }
-    if (N3) {  // the rows have fixed slots: the union proper is the other used candidates
-      const unsigned long long rm = __ballot(cid >= row0 && cid < row0 + nrow);
-      u &= ~rm;
-      if (lane == 0) s_rowm[c] = rm;
-    }
     if (lane == 0) s_used[c] = u;
   }
-  if (N3 && lane < R) atomicAdd(&s_fc[lane], fc);
   __syncthreads();
-  // 4) the union: used candidates in candidate order (slot = rank + 1); N3: the block's rows
-  // first (slot r + 1), then the other used candidates
+  // 4) the union: used candidates in candidate order (slot = rank + 1)
   int u = 0;
   {
     const int v = tid < nch ? __popcll(s_used[tid]) : 0;
     const int ex = blk_scan<NT>(v, s_sc, &u);
     if (tid < nch) s_upre[tid] = ex;
   }
-  const int ubase = N3 ? nrow : 0;
-  u += ubase;
-  if (N3 && tid < nrow) ulist[(size_t)b * ucap + tid] = row0 + tid;
   int ui_tot = 0;  // iu: the inner union, numbered in candidate order like the full one
   if (iu) {
     const int v = tid < nch ? __popcll(s_usedi[tid]) : 0;
@@ -757,15 +714,13 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
   }
   __syncthreads();
   // the union list, and each chunk's slot words: candidate l of chunk c, if used, has slot
-  // ubase + s_upre[c] + 1 + (used candidates below it); a row (N3) has slot r + 1
+  // s_upre[c] + 1 + (used candidates below it)
   for (int c = wv; c < nch; c += NW) {
     const unsigned long long used = s_used[c];
     const int below = blk_mbcnt(used);
-    int sl = ubase + s_upre[c] + 1 + below;
-    if (N3 && ((s_rowm[c] >> lane) & 1ull)) sl = s_cpos[c * 64 + lane] - row0 + 1;
-    s_q[c][lane] = (unsigned short)blk_q(sl, cq);
+    s_q[c][lane] = (unsigned short)blk_q(s_upre[c] + 1 + below, cq);
     if ((used >> lane) & 1ull)
-      ulist[(size_t)b * ucap + ubase + s_upre[c] + below] = s_cpos[c * 64 + lane];
+      ulist[(size_t)b * ucap + s_upre[c] + below] = s_cpos[c * 64 + lane];
     if (iu) {
       const unsigned long long usedi = s_usedi[c];
       if ((usedi >> lane) & 1ull)
@@ -797,34 +752,19 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
   static_assert(U * 16 <= 64, "a lane word of U 16-bit slots in 64 bits");
   const int r = wv * RPW + lane / LPR, part = lane % LPR;
   const bool live = r < nrow;
-  auto word0 = [&](int c, int sel) -> unsigned long long {
+  auto word = [&](int c, int sel) -> unsigned long long {
     return INNER ? s_w[(c * R + r) * 2 + sel] : s_w[c * R + r];
-  };
-  // N3: a row's entries that are rows of the block come first (virtual words 0 .. nch-1),
-  // then the others (nch .. 2 nch-1), each part in candidate order -- the pair passes meet a
-  // row's Newton-3 pairs in its first walk steps only
-  const int nv = N3 ? 2 * nch : nch;
-  auto word = [&](int v, int sel) -> unsigned long long {
-    if (!N3) return word0(v, sel);
-    const int c = v < nch ? v : v - nch;
-    const unsigned long long m = s_rowm[c];
-    return word0(c, sel) & (v < nch ? m : ~m);
-  };
-  // the slot words of candidate `bit` of (virtual) word v in table qt: s_q, or s_qi for
-  // the inner rows over their own union
-  auto qof = [&](const unsigned short (*qt)[64], int v, int bit) -> unsigned short {
-    return qt[(N3 && v >= nch) ? v - nch : v][bit];
   };
   bool over = false;
   auto emit = [&](int sel, unsigned short *__restrict__ rows, int *__restrict__ cnt_out) {
     int cnt = 0;
     if (live)
-      for (int c = 0; c < nch; c++) cnt += __popcll(word0(c, sel));
+      for (int c = 0; c < nch; c++) cnt += __popcll(word(c, sel));
     const int nchunk = min((cnt + UG - 1) / UG, sstride / UG);
     unsigned short *const out = rows + (size_t)(row0 + r) * sstride;
     const unsigned short(*const qt)[64] = (iu && sel == 1) ? s_qi : s_q;
-    int c = 0, acc = 0;  // (virtual) word c holds the entries from acc on
-    unsigned long long w = (live && nv > 0) ? word(0, sel) : 0ull;
+    int c = 0, acc = 0;  // word c holds the entries from acc on
+    unsigned long long w = (live && nch > 0) ? word(0, sel) : 0ull;
     for (int ch = part; ch < nchunk; ch += LPR) {
       const int e0 = ch * UG;
       while (acc + __popcll(w) <= e0) {  // (e0 < cnt: the word holding it exists)
@@ -846,7 +786,7 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
             while (m == 0ull) m = word(++cc, sel);
             const int bit = __ffsll((long long)m) - 1;
             m &= m - 1ull;
-            buf[l] |= (unsigned long long)qof(qt, cc, bit) << (16 * q);
+            buf[l] |= (unsigned long long)qt[cc][bit] << (16 * q);
           }
       if (U == 4) {
         ulonglong2 *const o = reinterpret_cast<ulonglong2 *>(out + e0);
@@ -862,34 +802,11 @@ k_blk_build(int n, QBins q, int dim, const double4 *__restrict__ xf,
     if (live && part == 0) {
       cnt_out[row0 + r] = cnt;
       over |= cnt > sstride;
-      if (sel == WS - 1) s_len[r] = cnt;
     }
   };
-  if (N3 && live && part == 0) fcnt[row0 + r] = s_fc[r];
-  if (bperm && tid < R) s_len[tid] = -1;
-  __syncthreads();
   emit(0, snbr, rcnt);
   if (INNER) emit(1, snbi, icnt);
   if (over) atomicMax(ovf, 1 << 21);
-  if (bperm) {
-    // the pair passes' row order inside the block: longest walked row (inner if built) first,
-    // so that a wave's rows -- walked to the longest of them -- have similar lengths
-    __syncthreads();
-    if (tid < R) {
-      const int my = s_len[tid];
-      int rank = 0;
-      for (int k = 0; k < R; k++) {
-        const int o = s_len[k];
-        rank += (o > my || (o == my && k < tid)) ? 1 : 0;
-      }
-      bperm[row0 + rank] = (unsigned char)tid;
-    }
-  }
-}
-
-// the block's lr-th walked row: the build's length order (bperm, k_blk_build) or in place
-__device__ __forceinline__ int blk_row(const unsigned char *bperm, int base, int lr) {
-  return bperm ? (int)bperm[base + lr] : lr;
 }
 
 // A lane's slot words: U = 2 slots in one 4-byte word, U = 4 in one 8-byte pair.
@@ -953,91 +870,24 @@ struct BlkSlots {
     }
   }
 };
-// walk2: the same slots, but each record is read by load(slot) and used by body(record); with
-// SPH_BLK_PIPE a lane's records of a chunk are all read before the first is used (U
-// independent pair evaluations in flight, the LDS latency covered by the next pairs' reads)
-#ifndef SPH_BLK_PIPE
-#define SPH_BLK_PIPE 1
-#endif
-template <int G, int U, int NCH, class Load, class Body>
-__device__ __forceinline__ void blk_walk2(BlkSlots<G, U, NCH> &sw, int c, int lane, Load load,
-                                          Body body) {
-  if (NCH > 0 && SPH_BLK_PIPE) {
-#pragma unroll
-    for (int k = 0; k < (NCH > 0 ? NCH : 1); k++) {
-      if (k * U * G >= c) break;
-      decltype(load(0)) r[U];
-#pragma unroll
-      for (int q = 0; q < U; q++)
-        if (k * U * G + q * G < c) r[q] = load(SlotWord<U>::get(sw.w[k], q));
-#pragma unroll
-      for (int q = 0; q < U; q++)
-        if (k * U * G + q * G < c) body(r[q]);
-    }
-  } else {
-    sw.walk(c, lane, [&](int q, bool) { body(load(q)); });
-  }
-}
-// walk3 (SPH_BLK_WALK = 1, NCH > 0): the same slots as one flat sequence of steps (step s:
+// walk3 (NCH > 0): the same slots as one flat sequence of steps (step s:
 // chunk s / U, position s % U), walked to the WAVE's longest row with scalar branches -- a
 // shorter row's extra steps read its padding (the sentinel slot, whose terms are exactly 0),
 // which costs nothing: a masked lane's issue slot is spent anyway -- and software-pipelined:
 // the records of steps s + 1 and s + 2 are read from LDS before step s is evaluated, so each
 // record's LDS latency is covered by two pair evaluations of the same wave (the LDS image
 // caps the pass at 4 waves per SIMD, which leaves the VGPRs for that).
-#ifndef SPH_BLK_WALK
-#define SPH_BLK_WALK 1
-#endif
-#ifndef SPH_BLK_ILP
-#define SPH_BLK_ILP 1  // (pair evaluations per scheduling group; 2: 0.288 vs 0.282 ms, 3: 0.375)
-#endif
+// pair evaluations per scheduling group (2: 0.288 vs 0.282 ms, 3: 0.375)
+constexpr int BLK_ILP = 1;
 template <class F, int... I>
 __device__ __forceinline__ void blk_steps_(F &&f, std::integer_sequence<int, I...>) {
   (void)(f(std::integral_constant<int, I>{}) && ...);
 }
-// Lane map of the pair passes (SPH_BLK_LMAP, G = 8): a ds_read_b128 serves a wave in four
-// 16-lane groups, {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32; each group holds
-// two whole rows instead of halves of four, so the 16 records it reads are two runs of 8
-// consecutive entries of two rows (consecutive union slots where a row's neighbours run
-// along a bin row: distinct banks) -- rows r = 0..3 of a half at lanes {0-3,12-15},
-// {20-27}, {4-11}, {16-19,28-31}.  A row's lanes are closed under xor 1, 2 and 12, so its
-// sums stay butterflies.
-#ifndef SPH_BLK_LMAP
-#define SPH_BLK_LMAP 0
-#endif
-template <int G>
-__device__ __forceinline__ int blk_lrow(int tid) {  // the workgroup-local row of thread tid
-  if constexpr (G == 8 && SPH_BLK_LMAP) {
-    const int p = tid & 31;
-    const int r = p < 4 ? 0 : p < 12 ? 2 : p < 16 ? 0 : p < 20 ? 3 : p < 28 ? 1 : 3;
-    return ((tid >> 5) << 2) + r;
-  } else {
-    return tid / G;
-  }
-}
-template <int G>
-__device__ __forceinline__ int blk_llane(int tid) {  // its lane in the row (entry order)
-  if constexpr (G == 8 && SPH_BLK_LMAP) {
-    const int p = tid & 31;
-    return p < 4 ? p : p < 12 ? p - 4 : p < 16 ? p - 8 : p < 20 ? p - 16 : p < 28 ? p - 20 : p - 24;
-  } else {
-    return tid & (G - 1);
-  }
-}
-template <int G>
-__device__ __forceinline__ double blk_row_sum(double v) {
-  if constexpr (G == 8 && SPH_BLK_LMAP) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    return v + __shfl_xor(v, 12, 64);
-  } else {
-    return group_sum<G>(v);
-  }
-}
+// the longest row count of the wave's rows (G lanes each), wave-uniform
 template <int G>
 __device__ __forceinline__ int wave_max_count(int c) {
 #pragma unroll
-  for (int d = (G == 8 && SPH_BLK_LMAP) ? 1 : G; d < 64; d <<= 1) c = max(c, __shfl_xor(c, d, 64));
+  for (int d = G; d < 64; d <<= 1) c = max(c, __shfl_xor(c, d, 64));
   return __builtin_amdgcn_readfirstlane(c);
 }
 // AHEAD = 0: no records read ahead (each group reads its own, fewer VGPRs -- for a pass
@@ -1050,7 +900,7 @@ __device__ __forceinline__ void blk_walk3(BlkSlots<G, U, NCH> &sw, int cmax, Loa
   if (cmax <= 0) return;
   typedef decltype(load(0)) Rec;
   if constexpr (AHEAD == 0) {
-    constexpr int IL = SPH_BLK_ILP, NG = (NS + IL - 1) / IL;
+    constexpr int IL = BLK_ILP, NG = (NS + IL - 1) / IL;
     auto group0 = [&](auto gc) -> bool {
       constexpr int g = decltype(gc)::value;
       if (g * IL * G >= cmax) return false;  // (wave-uniform)
@@ -1075,7 +925,7 @@ __device__ __forceinline__ void blk_walk3(BlkSlots<G, U, NCH> &sw, int cmax, Loa
   // A group runs whole once its first step is inside the wave's longest row (its later
   // steps may read only padding: exactly-zero terms).  The reads ahead are unconditional:
   // past a row's count its slot words hold the sentinel slot 0, a valid record.
-  constexpr int IL = SPH_BLK_ILP, NG = (NS + IL - 1) / IL;
+  constexpr int IL = BLK_ILP, NG = (NS + IL - 1) / IL;
   Rec r[2 * IL];
   blk_steps_([&](auto sc) -> bool {
     constexpr int s = decltype(sc)::value;
@@ -1127,9 +977,9 @@ k_blk_rhosum(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt,
              const int *__restrict__ rcnt, double4 *__restrict__ xf,
              const int *__restrict__ ty, double4 *__restrict__ vr,
              const Coefs *__restrict__ cf, int um, const unsigned short *__restrict__ snbi,
-             const int *__restrict__ icnt, const int *__restrict__ moved, int n3,
-             const unsigned char *__restrict__ bperm, const int *__restrict__ uilist,
-             const int *__restrict__ uicnt, const int *__restrict__ blist) {
+             const int *__restrict__ icnt, const int *__restrict__ moved,
+             const int *__restrict__ uilist, const int *__restrict__ uicnt,
+             const int *__restrict__ blist) {
   constexpr int NTH = R * G;
   if (snbi && *moved == 0) {  // (workgroup-uniform) the inner rows are still exact
     snbr = snbi;
@@ -1139,19 +989,12 @@ k_blk_rhosum(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt,
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char blk_smem[];
   __shared__ RhoPair s_c[NT1 ? 1 : NT2];
-  __shared__ double s_acc[R];  // n3: the later rows' shares (k_blk_build N3)
   const int nt1 = cf->ntypes + 1;
   // (blist: a subset of the blocks -- the interior or the boundary ones, overlap_on)
   const int b = blist ? blist[xcd_block()] : (int)xcd_block(), tid = threadIdx.x;
-  // (bperm: the block's rows in the build's length order, blk_row)
-  const int row = b * R + blk_row(bperm, b * R, blk_lrow<G>(tid)), lane = blk_llane<G>(tid);
+  const int row = b * R + tid / G, lane = tid & (G - 1);
   const bool live = row < n;
   const int rr = live ? row : n - 1;
-  // n3: slots 1 .. nrow are the block's rows (q <= qn3); a row's entries among them are the
-  // later rows, whose share (m_i W_ij) goes to their accumulator
-  const bool n3on = BLK_N3_BUILT && n3;
-  const int qn3 = n3on ? blk_q(min(R, n - b * R), CQ) : -1;
-  if (n3on && tid < R) s_acc[tid] = 0.0;
   // loads first: the row's count, the union's atom ids, then the row's slots and the
   // union's positions, so that one latency covers them all
   const int u = ucnt[b];
@@ -1219,22 +1062,12 @@ k_blk_rhosum(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt,
     wf = wf * wf;
     wf = wf * wf;
     acc = NT1 ? acc + wf : fma(cc.mK, wf, acc);
-    if (q > 0 && q <= qn3)  // a later row of this block: its share (cut and weight symmetric)
-      atomicAdd(&s_acc[sj - 1], NT1 ? wf : s_c[s_t[sj] * nt1 + it].mK * wf);
   };
-  if constexpr (NCH > 0 && SPH_BLK_WALK == 1) {
-    if (!n3on)
-      blk_walk3(sw, wave_max_count<G>(c), load, pair);
-    else
-      sw.walk(c, lane, [&](int q, bool) { pair(load(q)); });
-  } else {
+  if constexpr (NCH > 0)
+    blk_walk3(sw, wave_max_count<G>(c), load, pair);
+  else
     sw.walk(c, lane, [&](int q, bool) { pair(load(q)); });
-  }
-  acc = blk_row_sum<G>(acc);
-  if (n3on) {  // (workgroup-uniform) the earlier rows' shares of this row
-    __syncthreads();
-    acc += s_acc[blk_lrow<G>(tid)];
-  }
+  acc = group_sum<G>(acc);
   if (lane == 0 && live) {
     const double rho = ((cf->rho_keep >> it) & 1) ? vr[row].w
                                                    : cf->self_rho[it] + (NT1 ? c1.mK * acc : acc);
@@ -1403,18 +1236,6 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
 // EXP (study builds, SPH_EXP): 1 = neighbour records synthesised from the slot (no LDS
 // reads), 2 = LDS reads with a trivial body, 3 = no staging loads (LDS image left as is).
 // Outputs meaningless.
-// Occupancy the pair passes really get: the LDS image (~64 KiB at C2) admits two 512-thread
-// workgroups per CU, i.e. 4 waves per SIMD -- told to the compiler so that it schedules for
-// that (loads further ahead, up to 128 VGPRs) instead of for the 6-8 waves VGPRs alone allow
-#ifndef SPH_BLK_WPE
-#define SPH_BLK_WPE 0
-#endif
-#if SPH_BLK_WPE > 0
-#define SPH_BLK_OCC __attribute__((amdgpu_waves_per_eu(SPH_BLK_WPE, SPH_BLK_WPE)))
-#else
-#define SPH_BLK_OCC
-#endif
-
 #define SPH_BLK_FORCE_PARAMS                                                              \
   int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, int ucap,                 \
       const unsigned short *__restrict__ snbr, int sstride, const int *__restrict__ rcnt,     \
@@ -1423,12 +1244,11 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
       const Coefs *__restrict__ cf, double4 *__restrict__ fo, double *__restrict__ de,        \
       double gx, double gy, double gz, int um, int cq,                                        \
       const unsigned short *__restrict__ snbi, const int *__restrict__ icnt,                  \
-      const int *__restrict__ moved, int n3, const unsigned char *__restrict__ bperm,         \
-      const int *__restrict__ uilist, const int *__restrict__ uicnt,                          \
-      const int *__restrict__ blist
+      const int *__restrict__ moved, const int *__restrict__ uilist,                          \
+      const int *__restrict__ uicnt, const int *__restrict__ blist
 #define SPH_BLK_FORCE_ARGS                                                                \
   n, ulist, ucnt, ucap, snbr, sstride, rcnt, xf, vr, ty, en, cf, fo, de, gx, gy, gz, um, cq, \
-      snbi, icnt, moved, n3, bperm, uilist, uicnt, blist
+      snbi, icnt, moved, uilist, uicnt, blist
 // (the body of the force pass; the kernels below differ only in their occupancy request)
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, int AHEAD = 1>
 __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
@@ -1447,11 +1267,9 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   // multiply by viscC per pair.  viscC = 0 never gets here: the host launches VISC =
   // BLK_VISC_NONE then (no viscosity term, as viscC * ... = 0 in the reference)
   constexpr bool FOLDV = TAIT && !HEAT && NT1 && VISC == SPH_VISC_MONAGHAN;
-  constexpr int NA = HEAT ? 6 : 5;  // a row's shares: F (3), D, E [, EH]
   extern __shared__ __attribute__((aligned(16))) unsigned char blk_smem[];
   __shared__ TaitPair s_tp[(TAIT && !NT1) ? NT2 : 1];
   __shared__ HeatPair s_hp[(HEAT && !NT1) ? NT2 : 1];
-  __shared__ double s_acc[BLK_N3_BUILT ? R * NA : 1];  // n3: the later rows' shares
   const int nt1 = cf->ntypes + 1;
   const int b = blist ? blist[xcd_block()] : (int)xcd_block();  // (blist: a subset of blocks)
   const int tid = threadIdx.x;
@@ -1459,17 +1277,10 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   // the LDS image holds um union records (a multiple of 16); a larger union is walked in
   // WINDOWS of um records: each window staged in turn, every row walked against it with the
   // entries outside it read as the sentinel (workgroup-uniform; the host sizes um so that
-  // few blocks need it, and never with n3)
+  // few blocks need it)
   const int nwin = u > um ? (u + um - 1) / um : 1;
   const int u0 = min(u, um);
-  // n3: slots 1 .. nrow are the block's rows (q <= qn3); a row's entries among them are the
-  // later rows, whose shares go to their accumulators (Newton's third law: F and the heat
-  // term change sign, D and E do not)
-  const bool n3on = BLK_N3_BUILT && n3;
-  const int qn3 = n3on ? blk_q(min(R, n - b * R), CQ) : -1;
-  if (n3on)
-    for (int t = tid; t < R * NA; t += NTH) s_acc[t] = 0.0;
-  const int row = b * R + blk_row(bperm, b * R, blk_lrow<G>(tid)), lane = blk_llane<G>(tid);
+  const int row = b * R + tid / G, lane = tid & (G - 1);
   const bool live = row < n;
   const int rr = live ? row : n - 1;
   // loads first: the row's count, the union's atom ids, then the row's slots and the
@@ -1572,8 +1383,8 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
     const double rsq = rsq_t(dx, dy, dz);  // (+ 1e-300)
     const int pidx = NT1 ? 3 : it * nt1 + s_t[q];
     const double r = sqrt1n(rsq);
-    // this pair's terms (i side); a later row of the block takes its share too (n3)
-    double tfx = 0.0, tfy = 0.0, tfz = 0.0, tD = 0.0, tDj = 0.0, tE = 0.0, tEH = 0.0;
+    // this pair's terms (i side)
+    double tfx = 0.0, tfy = 0.0, tfz = 0.0, tD = 0.0, tE = 0.0, tEH = 0.0;
     if (TAIT) {
       const TaitPair cc = NT1 ? t1 : s_tp[pidx];
       const double d = fmax(cc.h - r, 0.0);
@@ -1605,7 +1416,6 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
         tE = sp * dvdr - sv * (velx * velx + vely * vely + velz * velz);
       }
       tD = NT1 ? dvdr * w : cc.mj * (dvdr * w);
-      tDj = NT1 ? tD : cc.mi * (dvdr * w);  // (the share of row j: m_i instead of m_j)
       fx += tfx;
       fy += tfy;
       fz += tfz;
@@ -1621,27 +1431,12 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
       tEH = NT1 ? t : cc.hmD * t;
       EH += tEH;
     }
-    if (q > 0 && q <= qn3) {
-      double *const a = s_acc + (blk_s<CQ>(q) - 1) * NA;
-      if (TAIT) {
-        atomicAdd(a + 0, -tfx);
-        atomicAdd(a + 1, -tfy);
-        atomicAdd(a + 2, -tfz);
-        atomicAdd(a + 3, tDj);
-        atomicAdd(a + 4, tE);
-      }
-      if (HEAT) atomicAdd(a + 5, -tEH);
-    }
   };
   auto walk = [&](auto ld) {
-    if constexpr (NCH > 0 && SPH_BLK_WALK == 1) {
-      if (!n3on)
-        blk_walk3<AHEAD>(sw, wave_max_count<G>(c), ld, pair);
-      else
-        blk_walk2(sw, c, lane, ld, pair);
-    } else {
-      blk_walk2(sw, c, lane, ld, pair);
-    }
+    if constexpr (NCH > 0)
+      blk_walk3<AHEAD>(sw, wave_max_count<G>(c), ld, pair);
+    else
+      sw.walk(c, lane, [&](int q, bool) { pair(ld(q)); });
   };
   if (nwin == 1) {
     walk(load);
@@ -1663,25 +1458,13 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
     }
   }
   if (TAIT) {
-    fx = blk_row_sum<G>(fx);
-    fy = blk_row_sum<G>(fy);
-    fz = blk_row_sum<G>(fz);
-    D = blk_row_sum<G>(D);
-    E = blk_row_sum<G>(E);
+    fx = group_sum<G>(fx);
+    fy = group_sum<G>(fy);
+    fz = group_sum<G>(fz);
+    D = group_sum<G>(D);
+    E = group_sum<G>(E);
   }
-  if (HEAT) EH = blk_row_sum<G>(EH);
-  if (n3on) {  // (workgroup-uniform) the earlier rows' shares of this row
-    __syncthreads();
-    const double *const a = s_acc + blk_lrow<G>(tid) * NA;
-    if (TAIT) {
-      fx += a[0];
-      fy += a[1];
-      fz += a[2];
-      D += a[3];
-      E += a[4];
-    }
-    if (HEAT) EH += a[5];
-  }
+  if (HEAT) EH = group_sum<G>(EH);
   if (lane == 0 && live) {
     double dE = 0.0;
     if (TAIT) {
@@ -1698,30 +1481,20 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
 }
 
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
-__global__ void __launch_bounds__(R * G) SPH_BLK_OCC k_blk_force(SPH_BLK_FORCE_PARAMS) {
+__global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
   blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP>(SPH_BLK_FORCE_ARGS);
 }
-// one type, taitwater alone (C2): asked for 5 waves per SIMD (<= 96 VGPRs, no spill) -- the
-// compiler otherwise settles at 98 VGPRs, 4 waves, while the LDS image admits 6
-// (0.2550 vs 0.272-0.273 ms per launch on one box, profiles/r05/README.md); the heat and
-// multi-type variants keep the default (at 96 VGPRs they would spill)
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
-__global__ void __launch_bounds__(R * G) __attribute__((amdgpu_waves_per_eu(5, 5)))
-k_blk_force_w5(SPH_BLK_FORCE_PARAMS) {
-  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP>(SPH_BLK_FORCE_ARGS);
-}
-// ... and at 6 waves per SIMD (<= 80 VGPRs: what the 49 KiB image allows, three workgroups
-// per CU) with no records read ahead -- the other waves cover the LDS latency: 0.2435 /
-// 0.2497 vs 0.2632 / 0.2627 ms per launch (two A/B pairs on one box, profiles/r05/README.md).
-// Production for C2; SPH_BLK_W6=0 (study) keeps the 5-wave kernel with the read-ahead.
+// one type, taitwater alone (C2): asked for 6 waves per SIMD (<= 80 VGPRs: what the 49 KiB
+// image allows, three workgroups per CU) with no records read ahead -- the other waves cover
+// the LDS latency.  The compiler otherwise settles at 98 VGPRs, 4 waves; 5 waves (<= 96
+// VGPRs) with the read-ahead measured 0.2550 vs 0.272-0.273 ms per launch, 6 waves 0.2435 /
+// 0.2497 vs 0.2632 / 0.2627 ms against that (profiles/r05/README.md).  The heat and
+// multi-type variants keep the default (at 96 VGPRs they would spill).
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
 __global__ void __launch_bounds__(R * G) __attribute__((amdgpu_waves_per_eu(6, 6)))
 k_blk_force_w6(SPH_BLK_FORCE_PARAMS) {
   blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 0>(SPH_BLK_FORCE_ARGS);
 }
-#ifndef SPH_BLK_W6
-#define SPH_BLK_W6 1
-#endif
 
 // blocks of a build whose union exceeds the force pass's LDS image (um records): the pass
 // walks them in windows of um union records (statistics only, sph_engine_stats blk_nbig)
@@ -1810,16 +1583,12 @@ struct BlkArgs {
   int exp = 0;          // study variants (SPH_EXP), 0 in production
   int cq = BLK_CH / 16;  // image chunk bytes / 16 (BLK_CHE / 16 with the heat term)
   const int *ulist = nullptr, *ucnt = nullptr, *rcnt = nullptr;
-  // the union the inner rows index: their own (iu: k_blk_build / k_blk_inner renumbered
-  // them) or the full one
+  // the inner rows' own union (k_blk_build / k_blk_inner renumber them over it)
   int *uilist = nullptr, *uicnt = nullptr;
-  bool iu = false;
   const unsigned short *snbr = nullptr;
   // inner rows (k_blk_inner) and the device flag that retires them; snbi == nullptr: none
   const unsigned short *snbi = nullptr;
   const int *icnt = nullptr, *moved = nullptr;
-  bool n3 = false;      // rows built with Newton-3 inside the blocks (k_blk_build N3)
-  const unsigned char *bperm = nullptr;  // the passes' row order per block (k_blk_build)
   // a subset of the blocks (nlist ids; the pair passes only): the interior or the boundary
   // blocks of a brick (k_blk_interior), so the interior ones run while the halos move
   const int *blist = nullptr;
@@ -1883,87 +1652,72 @@ inline void blk_neigh(int shape, bool big, bool nt1, hipStream_t s, int n, const
 }
 
 // k_blk_build (the default block build; k_blk_neigh remains the large-image fallback)
-template <int R, int G, int U, bool NT1, bool INNER, bool N3>
+template <int R, int G, int U, bool NT1, bool INNER>
 inline void blk_build_t(hipStream_t s, int n, const QBins &q, int dim, const double4 *xf,
                         const int *ty, const double4 *xb, const int *tb, const int *qbeg,
                         const Coefs *cf, int ucap, int sstride, int *ulist, int *ucnt,
                         int *rcnt, unsigned short *snbr, int *icnt, unsigned short *snbi,
-                        int *ovf, int *umax, int cq, int bexp, int *fcnt, unsigned char *bperm,
-                        int *uilist, int *uicnt, int *kcnt) {
+                        int *ovf, int *umax, int cq, int bexp, int *uilist, int *uicnt,
+                        int *kcnt) {
   // (bexp bit 8: the small candidate image, BLK_SCAP_S)
   const bool small = (bexp & 0x100) != 0;
   bexp &= 0xff;
 #ifdef SPH_STUDY
-  auto fn = bexp == 1 ? k_blk_build<R, G, U, NT1, INNER, N3, 1>
-          : bexp == 2 ? k_blk_build<R, G, U, NT1, INNER, N3, 2>
-          : bexp == 3 ? k_blk_build<R, G, U, NT1, INNER, N3, 3>
-          : bexp == 4 ? k_blk_build<R, G, U, NT1, INNER, N3, 4>
-          : small     ? k_blk_build<R, G, U, NT1, INNER, N3, 0, BLK_SCAP_S>
-                      : k_blk_build<R, G, U, NT1, INNER, N3, 0>;
+  auto fn = bexp == 1 ? k_blk_build<R, G, U, NT1, INNER, 1>
+          : bexp == 2 ? k_blk_build<R, G, U, NT1, INNER, 2>
+          : bexp == 3 ? k_blk_build<R, G, U, NT1, INNER, 3>
+          : bexp == 4 ? k_blk_build<R, G, U, NT1, INNER, 4>
+          : small     ? k_blk_build<R, G, U, NT1, INNER, 0, BLK_SCAP_S>
+                      : k_blk_build<R, G, U, NT1, INNER, 0>;
 #else
-  auto fn = small ? k_blk_build<R, G, U, NT1, INNER, N3, 0, BLK_SCAP_S>
-                  : k_blk_build<R, G, U, NT1, INNER, N3, 0>;
+  auto fn = small ? k_blk_build<R, G, U, NT1, INNER, 0, BLK_SCAP_S>
+                  : k_blk_build<R, G, U, NT1, INNER, 0>;
 #endif
   hipLaunchKernelGGL(fn, dim3(blk_blocks(n, R)), dim3(256), 0, s, n, q, dim, xf, ty, xb, tb,
                      qbeg, cf, ucap, sstride, ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq,
-                     fcnt, bperm, uilist, uicnt, kcnt);
+                     uilist, uicnt, kcnt);
   hipLaunchKernelGGL(k_blk_stats, dim3(1), dim3(1024), 0, s, blk_blocks(n, R), ucnt, kcnt,
                      uicnt, umax);
 }
-template <int R, int G, int U, bool N3>
-inline void blk_build_n(bool nt1, bool inner, hipStream_t s, int n, const QBins &q, int dim,
+template <int R, int G, int U>
+inline void blk_build_s(bool nt1, bool inner, hipStream_t s, int n, const QBins &q, int dim,
                         const double4 *xf, const int *ty, const double4 *xb, const int *tb,
                         const int *qbeg, const Coefs *cf, int ucap, int sstride, int *ulist,
                         int *ucnt, int *rcnt, unsigned short *snbr, int *icnt,
-                        unsigned short *snbi, int *ovf, int *umax, int cq, int bexp, int *fcnt,
-                        unsigned char *bperm, int *uilist, int *uicnt, int *kcnt) {
+                        unsigned short *snbi, int *ovf, int *umax, int cq, int bexp,
+                        int *uilist, int *uicnt, int *kcnt) {
   if (nt1 && inner)
-    blk_build_t<R, G, U, true, true, N3>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                         ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
-                                         fcnt, bperm, uilist, uicnt, kcnt);
+    blk_build_t<R, G, U, true, true>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
+                                     ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
+                                     uilist, uicnt, kcnt);
   else if (nt1)
-    blk_build_t<R, G, U, true, false, N3>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                          ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq,
-                                          bexp, fcnt, bperm, uilist, uicnt, kcnt);
+    blk_build_t<R, G, U, true, false>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
+                                      ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
+                                      uilist, uicnt, kcnt);
   else if (inner)
-    blk_build_t<R, G, U, false, true, N3>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                          ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq,
-                                          bexp, fcnt, bperm, uilist, uicnt, kcnt);
+    blk_build_t<R, G, U, false, true>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
+                                      ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
+                                      uilist, uicnt, kcnt);
   else
-    blk_build_t<R, G, U, false, false, N3>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap,
-                                           sstride, ulist, ucnt, rcnt, snbr, icnt, snbi, ovf,
-                                           umax, cq, bexp, fcnt, bperm, uilist, uicnt, kcnt);
+    blk_build_t<R, G, U, false, false>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
+                                       ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
+                                       uilist, uicnt, kcnt);
 }
-// n3: Newton-3 inside the blocks (rows first in the union, the later rows' share; fcnt gets
-// the full counts)
-inline void blk_build(int shape, bool nt1, bool inner, bool n3, hipStream_t s, int n,
-                      const QBins &q, int dim, const double4 *xf, const int *ty,
-                      const double4 *xb, const int *tb, const int *qbeg, const Coefs *cf,
-                      int ucap, int sstride, int *ulist, int *ucnt, int *rcnt,
-                      unsigned short *snbr, int *icnt, unsigned short *snbi, int *ovf, int *umax,
-                      int cq, int bexp, int *fcnt, unsigned char *bperm, int *uilist,
+inline void blk_build(int shape, bool nt1, bool inner, hipStream_t s, int n, const QBins &q,
+                      int dim, const double4 *xf, const int *ty, const double4 *xb,
+                      const int *tb, const int *qbeg, const Coefs *cf, int ucap, int sstride,
+                      int *ulist, int *ucnt, int *rcnt, unsigned short *snbr, int *icnt,
+                      unsigned short *snbi, int *ovf, int *umax, int cq, int bexp, int *uilist,
                       int *uicnt, int *kcnt) {
-#ifdef SPH_STUDY
-#define SPH_IF_N3(R, G, U)                                                                  \
-  if (n3)                                                                                 \
-    blk_build_n<R, G, U, true>(nt1, inner, s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap,    \
-                               sstride, ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, \
-                               bexp, fcnt, bperm, uilist, uicnt, kcnt);                           \
-  else
-#else
-#define SPH_IF_N3(R, G, U) (void)n3;
-#endif
   switch (shape) {
-#define SPH_CASE(k, R, G, U)                                                                \
-  case k:                                                                                 \
-    SPH_IF_N3(R, G, U)                                                                    \
-    blk_build_n<R, G, U, false>(nt1, inner, s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap,   \
-                                sstride, ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, \
-                                bexp, fcnt, bperm, uilist, uicnt, kcnt);                          \
+#define SPH_CASE(k, R, G, U)                                                                 \
+  case k:                                                                                  \
+    blk_build_s<R, G, U>(nt1, inner, s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride, \
+                         ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp, uilist,   \
+                         uicnt, kcnt);                                                       \
     break;
     SPH_BLK_SHAPES(SPH_CASE)
 #undef SPH_CASE
-#undef SPH_IF_N3
   }
 }
 
@@ -1979,7 +1733,7 @@ inline void blk_rhosum_t(hipStream_t s, const BlkArgs &k, double4 *xf, const int
   if (nb == 0) return;
   hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt,
                      k.ucap, k.snbr, k.sstride, k.rcnt, xf, ty, vr, cf, k.um, k.snbi, k.icnt,
-                     k.moved, k.n3 ? 1 : 0, k.bperm, k.uilist, k.uicnt, k.blist);
+                     k.moved, k.uilist, k.uicnt, k.blist);
 }
 template <int R, int G, int U>
 inline void blk_rhosum_s(bool nt1, hipStream_t s, const BlkArgs &k, double4 *xf, const int *ty,
@@ -2008,10 +1762,8 @@ inline void blk_rhosum(bool nt1, hipStream_t s, const BlkArgs &k, double4 *xf, c
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
 inline void blk_force_t(hipStream_t s, const BlkArgs &k, const RowArgs &a) {
   auto fn = [] {
-    if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0 && SPH_BLK_WPE == 0 && SPH_BLK_W6)
+    if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0)
       return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP>;
-    else if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0 && SPH_BLK_WPE == 0)
-      return k_blk_force_w5<R, G, U, NCH, VISC, MODE, NT1, EXP>;
     else
       return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP>;
   }();
@@ -2026,8 +1778,8 @@ inline void blk_force_t(hipStream_t s, const BlkArgs &k, const RowArgs &a) {
   if (nb == 0) return;
   hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt,
                      k.ucap, k.snbr, k.sstride, k.rcnt, a.xf, a.vr, a.ty, a.en, a.cf, a.fo,
-                     a.de, a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved,
-                     k.n3 ? 1 : 0, k.bperm, k.uilist, k.uicnt, k.blist);
+                     a.de, a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved, k.uilist,
+                     k.uicnt, k.blist);
 }
 
 // the inner rows of a build (k_blk_inner): same launch geometry and LDS image as rhosum
@@ -2051,8 +1803,7 @@ inline void blk_inner_t(hipStream_t s, const BlkArgs &k, const double4 *xf, cons
   const int nb = blk_blocks(k.n, R);
   hipLaunchKernelGGL(fn, dim3(rf.cond ? std::min(nb, 512) : nb), dim3(R * G), lds, s, k.n,
                      k.ulist, k.ucnt, k.ucap, k.snbr, k.sstride, k.rcnt, xf, ty, cf, snbi, icnt,
-                     k.um, rf.cond, rf.zero, rf.x0, k.iu ? k.uilist : nullptr,
-                     k.iu ? k.uicnt : nullptr, rf.umax);
+                     k.um, rf.cond, rf.zero, rf.x0, k.uilist, k.uicnt, rf.umax);
 }
 template <int R, int G, int U>
 inline void blk_inner_s(bool nt1, hipStream_t s, const BlkArgs &k, const double4 *xf,

@@ -21,9 +21,6 @@
 #include "sph_comm.h"
 #include "sph_dispatch.h"
 #include "sph_blk_kernels.h"
-#ifdef SPH_STUDY  // (k_blk_build2: measured slower, study builds only)
-#include "sph_blk_build2.h"
-#endif
 #include "sph_engine_kernels.h"
 #include "sph_engine_mp.h"
 #include "sph_fix_kernels.h"
@@ -73,20 +70,6 @@ static bool row2_lp() {
   static bool v = study_int("SPH_LP", 1) != 0;
   return v;
 }
-// SPH_TIGHT (default 0): with a strided list, the rhosum pass writes this step's in-cut
-// list (k_row2_rhosum TIGHT) and the force pass walks it instead of the full list.
-// Measured on C2 1M: taitwater 0.57 -> 0.46 ms but rhosum 0.31 -> 0.48 ms (the stores
-// count in vmcnt, so the loop waits for them with the prefetched indices) -> off.
-static bool tight_on() {
-  static bool v = study_int("SPH_TIGHT", 0) != 0;
-  return v;
-}
-// SPH_PI (default 0): pair-interleaved entry slots with lane-pair gathers (entry_slot).
-// Measured on C2 1M: taitwater 0.562 (off) vs 0.567 ms (on), rhosum equal -> off.
-static bool row2_pi() {
-  static bool v = study_int("SPH_PI", 0) != 0 && row2_lp();
-  return v;
-}
 static bool row2_iv() {
   static bool v = study_int("SPH_IV", 1) != 0;
   return v;
@@ -94,13 +77,6 @@ static bool row2_iv() {
 // SPH_EXP: study variants of the pair passes (tools/kernel_sweep.py sets it for the timed
 // passes only, so it is read per launch); 0 in production
 static int row2_exp() { return study_int("SPH_EXP", 0); }
-// SPH_OVERLAP (default 0): with a brick decomposition, run the pair passes of interior
-// rows (no ghost in the list) on a second stream while the forward / rho halos are in
-// flight, then the boundary rows after them (sph_engine::pair_compute_overlap).  Parity
-// holds (tests/test_gpu_bricks.py with SPH_OVERLAP=1), but on one GPU through the RCCL
-// loopback it measured 1.29 (serial) -> 1.35 ms per step at C2 1M: the split launches
-// cost more than the loopback halo they hide.  Whether xGMI transfers (~17 MB per step
-// per rank at C4) change that is unmeasured here (no multi-GPU box) -> off by default.
 // SPH_TBITS (default 1): with several types, strided list entries carry the neighbour's
 // type in their top bits, so the row2 passes skip the per-neighbour type gather
 static bool tbits_env() {
@@ -136,34 +112,10 @@ static bool mp_typed_env() {
   static bool v = study_int("SPH_MP_TYPED", 1) != 0;
   return v;
 }
-// one brick's borders: a dimension's two swaps in three launches (k_brd_*), or the
-// per-swap flags + select + append of earlier rounds (SPH_BRD_FUSED=0, builds)
-#ifndef SPH_BRD_FUSED
-#define SPH_BRD_FUSED 1
-#endif
-// SPH_ROWSORT (study builds; default 0): the pair passes walk each block's rows longest
-// first (k_blk_build's per-block order), so that a wave's rows have similar lengths
-static bool rowsort() {
-#ifndef SPH_ROWSORT_DEFAULT
-#define SPH_ROWSORT_DEFAULT 0  // (on: force 0.291 vs 0.287 ms, rhosum 0.123 vs 0.111, profiles/r04/rowsort)
-#endif
-  static bool v = study_int("SPH_ROWSORT", SPH_ROWSORT_DEFAULT) != 0;
-  return v;
-}
-// SPH_N3 (study builds only; default 0): the block build keeps each pair of rows of one
-// block once (Newton-3 inside the blocks, k_blk_build N3) -- measured slower, DESIGN.md 5.2
 // SPH_INNER_REFRESH (study builds; default 1): derive the inner rows again between rebuilds
 // once an atom has moved past their margin (refresh_inner)
-static bool inner_inline() {
-  static bool v = study_int("SPH_INNER_INLINE", 1) != 0;
-  return v;
-}
 static bool refresh_env() {
   static bool v = study_int("SPH_INNER_REFRESH", 1) != 0;
-  return v;
-}
-static bool n3_env() {
-  static bool v = BLK_N3_BUILT && study_int("SPH_N3", 0) != 0;
   return v;
 }
 // SPH_MP_RHOFUSE (default 1): the multiphase engine's list fill sums rhosum/multiphase over
@@ -326,10 +278,7 @@ struct sph_engine {
   bool strided = false;    // list in fixed-stride rows (row i at i*list_stride, ccnt[i])
   int list_stride = 0;
   int list_perm_g = 0;     // strided rows stored chunk-transposed for G-lane rows (tpos)
-  int list_perm_pi = 0;    // ... with pair-interleaved entry slots
   bool list_tbits = false; // strided entries carry the neighbour's type (SPH_TBIT_SHIFT)
-  // this step's in-cut ("tight") list, written by the rhosum pass for the force pass
-  DBuf<int> tnbr, tcnt;
   // block-staged path (production, sph_blk_kernels.h): per block of consecutive rows its
   // union of neighbour atoms (ulist, ucnt) and the rows' 16-bit slot rows (snbr)
   bool blk = false;
@@ -340,25 +289,15 @@ struct sph_engine {
   DBuf<int> uilist, uicnt;
   bool blk_ksmall = false;  // k_blk_build with the small candidate image (BLK_SCAP_S)
   int blk_kover = 0;        // ... builds it overflowed
-  bool blk_iu = false;  // (the inner rows index uilist; else the full union)
   // ... and the inner rows of the build (k_blk_inner: pairs within cut + inner_margin), the
   // owned positions they were written at and the flag that retires them (sc.x0 / sc.moved)
   DBuf<unsigned short> snbi;
   DBuf<int> icnt, moved;
-  // the pair passes' row order inside each block (longest row first, k_blk_build)
-  DBuf<unsigned char> bperm;
-  bool blk_perm = false;
-  unsigned char *bperm_buf(int nb, int R) {
-    bperm.reserve((size_t)nb * R);
-    return bperm.p;
-  }
   DBuf<double4> x0;
   double inner_margin = 0.0;
   bool inner = false, inner_written = false;  // (written: by k_blk_build, with the full rows)
   DBuf<int> nbs;  // fixed-stride scratch rows of a CSR build (list_q)
   DBuf<int> mx, ccnt;  // scratch scalars; full-list row counts of the current build
-  DBuf<int> pcnt;      // block path with Newton-3 (blk_n3): the rows' stored counts
-  bool blk_n3 = false;
   DBuf<long long> blen;
   // cub scratch
   DBuf<unsigned char> tmp;
@@ -632,26 +571,11 @@ struct sph_engine {
         // peers' are read back together below: one host sync per dimension
         nsel.reserve(2);
         sw.list.reserve(nlast > 0 ? nlast : 1);
-        if (SPH_BRD_FUSED) {
-          sw.lo_sel = sendflag ? sw.lo : 1.0;  // (no send: an empty slab)
-          sw.hi_sel = sendflag ? sw.hi : 0.0;
-        } else if (sendflag && nlast > 0) {
-          flags.reserve(nlast);
-          hipLaunchKernelGGL(k_slab_flags, dim3(blocks(nlast)), dim3(BLK), 0, s, nlast, d,
-                             sw.lo, sw.hi, xf.p, flags.p);
-          hipcub::CountingInputIterator<int> it(0);
-          size_t tb = 0;
-          SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flags.p, sw.list.p,
-                                                    nsel.p + dir, nlast, s));
-          tmp_reserve(tb);
-          SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, flags.p, sw.list.p,
-                                                    nsel.p + dir, nlast, s));
-        } else {
-          SPH_HIP_TRY(hipMemsetAsync(nsel.p + dir, 0, sizeof(int), s));
-        }
+        sw.lo_sel = sendflag ? sw.lo : 1.0;  // (no send: an empty slab)
+        sw.hi_sel = sendflag ? sw.hi : 0.0;
       }
       Swap &a = *pair[0], &b = *pair[1];
-      if (SPH_BRD_FUSED) {  // both swaps' selections in three launches
+      {  // both swaps' selections in three launches
         const int nb = (nlast + BRD_CH - 1) / BRD_CH;
         if (nb == 0) {
           SPH_HIP_TRY(hipMemsetAsync(nsel.p, 0, 2 * sizeof(int), s));
@@ -1229,22 +1153,18 @@ struct sph_engine {
       gcap_hint = (int)std::min(1.5 * (out / in - 1.0) * nlocal + 4096.0, 2.0e9 - nlocal);
     }
     gnall.reserve(nsw + 2);
-    nsel.reserve(nsw + 1);
     for (;;) {
       const int gcap = gcap_hint, cap = nlocal + gcap;
       ensure_atoms((size_t)cap, true);
       gowner.reserve(gcap, true, s);
       gimg.reserve(gcap, true, s);
       if (pc) gsrc.reserve(gcap, true, s);
-      flags.reserve(cap);
-      sel.reserve(cap);
       h_small[14] = nlocal;  // (pinned; the read-back below lands in words 0 .. nsw + 1)
       h_small[15] = 0;       // the overflow word
       SPH_HIP_TRY(hipMemcpyAsync(gnall.p, h_small + 14, sizeof(int), hipMemcpyHostToDevice, s));
       SPH_HIP_TRY(hipMemcpyAsync(gnall.p + nsw + 1, h_small + 15, sizeof(int),
                                  hipMemcpyHostToDevice, s));
       int w = 0;
-#if SPH_BRD_FUSED
       // a dimension's two swaps in three launches (k_brd_count / scan / scatter)
       for (int d = 0; d < ndim; d++) {
         if (!cfg.periodic[d]) continue;  // sendneed = 0 across a non-periodic boundary
@@ -1263,41 +1183,6 @@ struct sph_engine {
                            mp ? cvv.p : (double *)nullptr, mp ? cg.p : (double4 *)nullptr);
         w += 2;
       }
-#else
-      for (int d = 0; d < ndim; d++) {
-        if (!cfg.periodic[d]) continue;  // sendneed = 0 across a non-periodic boundary
-        const int *const nlast = gnall.p + w;  // both swaps scan the atoms before this dim
-        for (int ineed = 0; ineed < 2; ineed++, w++) {
-          double lo, hi;
-          int pbc;
-          if (ineed == 0) {
-            lo = -1.0e20;
-            hi = sublo[d] + cutghost;
-            pbc = 1;
-          } else {
-            lo = subhi[d] - cutghost;
-            hi = 1.0e20;
-            pbc = -1;
-          }
-          const double shift = pbc * box.prd[d];
-          hipLaunchKernelGGL(k_slab_flags_dev, dim3(blocks(cap)), dim3(BLK), 0, s, cap, nlast,
-                             d, lo, hi, xf.p, flags.p);
-          hipcub::CountingInputIterator<int> it(0);
-          size_t tb = 0;
-          SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flags.p, sel.p, nsel.p + w,
-                                                    cap, s));
-          tmp_reserve(tb);
-          SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, flags.p, sel.p, nsel.p + w,
-                                                    cap, s));
-          hipLaunchKernelGGL(k_append_ghosts_dev, dim3(blocks(gcap)), dim3(BLK), 0, s, gcap,
-                             nsel.p + w, sel.p, nlocal, gnall.p + w, cap, d, pbc, shift, xf.p,
-                             vr.p, en.p, ty.p, gowner.p, gimg.p, pc ? gsrc.p : (int *)nullptr,
-                             mp ? vel.p : (double4 *)nullptr, mp ? rm.p : (double *)nullptr,
-                             mp ? cvv.p : (double *)nullptr, mp ? cg.p : (double4 *)nullptr,
-                             gnall.p + nsw + 1);
-        }
-      }
-#endif
       SPH_HIP_TRY(hipMemcpyAsync(h_small, gnall.p, (nsw + 2) * sizeof(int),
                                  hipMemcpyDeviceToHost, s));
       SPH_HIP_TRY(hipStreamSynchronize(s));
@@ -1483,31 +1368,31 @@ struct sph_engine {
       const bool t = nt1();
       int *const cnt_out = (!fill || stride > 0) ? ccnt.p : (int *)nullptr;
       int *const rows = dst ? dst : nbr.p;
-#define SPH_N3P(F, T, P)                                                                       \
+#define SPH_NGHP(F, T, P)                                                                       \
   hipLaunchKernelGGL((k_neigh3<G, 4, F, T, false, P>), grid, block, 0, s, n, qb, cfg.dim,       \
                      xi_src, ty.p,                                                             \
                      xb.p, tb.p, qbeg.p, dc, cnt_out,                                          \
                      (F && stride == 0) ? off.p : (const int *)nullptr,                        \
                      F ? rows : (int *)nullptr, stride, mx.p, stride > 0 ? list_perm_g : 0,    \
-                     list_perm_pi, mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0))
-#define SPH_N3R(T)                                                                             \
+                     mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0))
+#define SPH_NGHR(T)                                                                             \
   hipLaunchKernelGGL((k_neigh3<G, 4, true, T, true, true>), grid, block, 0, s, n, qb, cfg.dim,  \
                      xi_src,                                                                   \
                      ty.p, xb.p, tb.p, qbeg.p, dc, cnt_out,                                    \
-                     stride == 0 ? off.p : (const int *)nullptr, rows, stride, mx.p, 0, 0, 2, \
+                     stride == 0 ? off.p : (const int *)nullptr, rows, stride, mx.p, 0, 2,    \
                      dm, rm.p, rho_tmp.p)
       // (mp: xb packs the types, k_bin_copy tpack)
-#define SPH_N3(F, T)                                                                           \
+#define SPH_NGH(F, T)                                                                           \
   do {                                                                                        \
-    if (mp) SPH_N3P(F, T, true);                                                              \
-    else SPH_N3P(F, T, false);                                                                \
+    if (mp) SPH_NGHP(F, T, true);                                                              \
+    else SPH_NGHP(F, T, false);                                                                \
   } while (0)
-      if (fill && rho) { if (t) SPH_N3R(true); else SPH_N3R(false); }
-      else if (fill) { if (t) SPH_N3(true, true); else SPH_N3(true, false); }
-      else { if (t) SPH_N3(false, true); else SPH_N3(false, false); }
-#undef SPH_N3
-#undef SPH_N3P
-#undef SPH_N3R
+      if (fill && rho) { if (t) SPH_NGHR(true); else SPH_NGHR(false); }
+      else if (fill) { if (t) SPH_NGH(true, true); else SPH_NGH(true, false); }
+      else { if (t) SPH_NGH(false, true); else SPH_NGH(false, false); }
+#undef SPH_NGH
+#undef SPH_NGHP
+#undef SPH_NGHR
     };
     mx.reserve(8);
     // single pass into fixed-stride rows when a previous build sized them and nothing
@@ -1519,7 +1404,6 @@ struct sph_engine {
       // rows stored chunk-transposed for the row2 kernels' 16-B index loads; with several
       // types the neighbour's type rides in the entry's top bits
       list_perm_g = (row2_iv() && !mp) ? row2_iv_g() : 0;
-      list_perm_pi = (row2_pi() && !mp) ? 1 : 0;
       list_tbits = !nt1() && tbits_env() && !mp;
       nbr.reserve((size_t)n * list_stride);
       SPH_HIP_TRY(hipMemsetAsync(mx.p, 0, sizeof(int), s));
@@ -1540,7 +1424,6 @@ struct sph_engine {
     bool filled = false;
     if (!sover && list_stride > 0 && (long)n * list_stride < 0x7fffffffL) {
       list_perm_g = 0;
-      list_perm_pi = 0;
       nbs.reserve((size_t)n * list_stride);
       SPH_HIP_TRY(hipMemsetAsync(mx.p, 0, sizeof(int), s));
       launch(true, list_stride, nbs.p);
@@ -1605,9 +1488,6 @@ struct sph_engine {
     const int n = nlocal;
     const BlkShape sh = blk_shape(shape);
     const int chunk = sh.G * sh.U;
-    // k_blk_build2 (group candidate lists, sph_blk_build2.h): measured slower than
-    // k_blk_build (1.37 vs 1.11 ms at C2 1M, profiles/r05/README.md) -> study builds only
-    bool try2 = study_int("SPH_BUILD2", 0) != 0;
     for (int attempt = 0; attempt < 3; attempt++) {
       blk_sstride = (std::max(blk_rowcap, 1) + chunk - 1) / chunk * chunk;
       snbr.reserve((size_t)n * blk_sstride + 2 * chunk);  // + the pair passes' prefetch pad
@@ -1617,51 +1497,28 @@ struct sph_engine {
       kcnt.reserve(nb);
       SPH_HIP_TRY(hipMemsetAsync(mx.p, 0, 10 * sizeof(int), s));
       // k_blk_build (ballots, inner rows in the same pass); the bitmap walk k_blk_neigh for
-      // the large candidate image (and in study builds, SPH_BUILD=0)
-      const bool v2 = !big && study_int("SPH_BUILD", 1) != 0;
-      // the inner rows' ballots inside the build (SPH_INNER_INLINE, study; default 1), or a
-      // k_blk_inner pass over the full rows afterwards (build_inner)
-      const bool want_inner = inner_margin > 0.0 && inner_inline();
+      // the large candidate image, with a k_blk_inner pass over the full rows afterwards
+      // (build_inner)
+      const bool v2 = !big;
+      const bool want_inner = inner_margin > 0.0;
       if (want_inner) {
         snbi.reserve((size_t)n * blk_sstride + 2 * chunk);
         icnt.reserve(n);
         uilist.reserve((size_t)nb * BLK_UCAP);
         uicnt.reserve(nb);
       }
-      // Newton-3 inside the blocks (k_blk_build N3): the passes walk the stored rows (pcnt),
-      // ccnt keeps the full counts
-      blk_n3 = v2 && n3_env();
-      if (blk_n3) pcnt.reserve(n + 1);
-      // the inner rows over their own union (not with N3: its rows-first union)
-#ifdef SPH_NO_IU  // (A/B builds: inner rows over the full union)
-      const bool iu = false;
-#else
-      const bool iu = v2 && want_inner && !blk_n3;
-#endif
-      // the group-list build (sph_blk_build2.h) unless a study variant needs k_blk_build
-      const bool v3 = v2 && try2 && !blk_n3 && !rowsort();
-#ifdef SPH_STUDY
-      if (v3)
-        blk_build2(shape, nt1(), want_inner, s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p, qbeg.p,
-                   dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p, ccnt.p, snbr.p, icnt.p, snbi.p,
-                   mx.p, mx.p + 1, blk_cq(), iu ? uilist.p : nullptr, iu ? uicnt.p : nullptr,
-                   kcnt.p);
-      else
-#endif
+      // the inner rows over their own union
+      const bool iu = v2 && want_inner;
       if (v2)
-        blk_build(shape, nt1(), want_inner, blk_n3, s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p,
-                  qbeg.p, dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p,
-                  blk_n3 ? pcnt.p : ccnt.p, snbr.p, icnt.p, snbi.p, mx.p, mx.p + 1, blk_cq(),
-                  study_int("SPH_BEXP", 0) | (blk_ksmall ? 0x100 : 0), ccnt.p,
-                  rowsort() ? bperm_buf(nb, sh.R) : nullptr,
+        blk_build(shape, nt1(), want_inner, s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p, qbeg.p,
+                  dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p, ccnt.p, snbr.p, icnt.p, snbi.p,
+                  mx.p, mx.p + 1, blk_cq(), study_int("SPH_BEXP", 0) | (blk_ksmall ? 0x100 : 0),
                   iu ? uilist.p : nullptr, iu ? uicnt.p : nullptr, kcnt.p);
       else
         blk_neigh(shape, big, nt1(), s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p, qbeg.p, xpos.p,
                   dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p, ccnt.p, snbr.p, mx.p, mx.p + 1,
                   blk_cq(), study_int("SPH_BEXP", 0));
       inner_written = v2 && want_inner;
-      blk_iu = iu;
-      blk_perm = v2 && !blk_n3 && rowsort();
       // the build's statistics: ONE read-back
       int *const hm = h_small;
       SPH_HIP_TRY(hipMemcpyAsync(hm, mx.p, 9 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1672,10 +1529,6 @@ struct sph_engine {
                 "candidates max %d mean %.1f\n",
                 shape, big ? " (large image)" : "", n, blk_rowcap, hm[0], hm[1], (double)hm[4] / nb, hm[2],
                 (double)hm[3] / nb);
-      if (hm[0] == (1 << 23)) {  // a group list outgrew k_blk_build2's: k_blk_build
-        try2 = false;
-        continue;
-      }
       if (hm[0] == (1 << 24)) {  // a block outgrew the small candidate image
         blk_ksmall = false;
         blk_kover++;
@@ -1695,7 +1548,7 @@ struct sph_engine {
       // the next build takes the small candidate image (four workgroups per CU) while this
       // one's largest block fits it (hm[2]: the largest candidate set; the blocks' sets move
       // by a few candidates between rebuilds); after two overflows it stays with the large one
-      if (v2 && !v3) blk_ksmall = blk_kover < 2 && hm[2] <= BLK_SCAP_S - 24;
+      if (v2) blk_ksmall = blk_kover < 2 && hm[2] <= BLK_SCAP_S - 24;
       // the largest union's force-pass LDS image (+ the static coefficient tables) must fit
       // the CU's 160 KiB
       blk_sh = shape;
@@ -1736,10 +1589,9 @@ struct sph_engine {
     const int m16 = std::max(16, (maxu + 15) / 16 * 16);
     int umf;
     if (fits(m16, 3)) umf = m16;
-    else if (blk_n3) umf = std::min(m16, cap(1));  // (study N3: no windows)
     else if (meanu * 1.10 <= cap(3)) umf = cap(3);
     else umf = std::min(m16, cap(2));
-    if (blkumf > 0 && !blk_n3) umf = std::min(umf, std::max(16, blkumf / 16 * 16));
+    if (blkumf > 0) umf = std::min(umf, std::max(16, blkumf / 16 * 16));
     return umf;
   }
   BlkArgs blk_args() const {
@@ -1754,17 +1606,14 @@ struct sph_engine {
     k.sstride = blk_sstride;
     k.ulist = ulist.p;
     k.ucnt = ucnt.p;
-    k.rcnt = blk_n3 ? pcnt.p : ccnt.p;
-    k.n3 = blk_n3;
-    k.bperm = blk_perm ? bperm.p : nullptr;
+    k.rcnt = ccnt.p;
     k.snbr = snbr.p;
     if (inner) {
       k.snbi = snbi.p;
       k.icnt = icnt.p;
       k.moved = moved_flag();
-      k.iu = blk_iu;
-      k.uilist = blk_iu ? uilist.p : ulist.p;
-      k.uicnt = blk_iu ? uicnt.p : ucnt.p;
+      k.uilist = uilist.p;
+      k.uicnt = uicnt.p;
     }
     return k;
   }
@@ -1827,11 +1676,8 @@ struct sph_engine {
     moved.reserve(2);
     const size_t nx0 = (size_t)nlocal + (multi() ? nghost : 0);
     x0.reserve(nx0);
-    if (!inner_written) {  // (k_blk_inner writes the inner unions too)
-      blk_iu = true;
-      BlkArgs k = blk_args();
-      blk_inner(nt1(), s, k, xf.p, ty.p, dc, snbi.p, icnt.p);
-    }
+    if (!inner_written)  // (k_blk_inner writes the inner unions too)
+      blk_inner(nt1(), s, blk_args(), xf.p, ty.p, dc, snbi.p, icnt.p);
     SPH_HIP_TRY(hipMemcpyAsync(x0.p, xf.p, nx0 * sizeof(double4), hipMemcpyDeviceToDevice, s));
     SPH_HIP_TRY(hipMemsetAsync(moved.p, 0, 2 * sizeof(int), s));
     sc.x0 = x0.p;
@@ -1865,8 +1711,8 @@ struct sph_engine {
   }
 
   bool overlap_on() const {
-    return multi() && overlap && (blk || use_row2()) && !tight_on() &&
-           (force_mode & M_TAIT) != 0 && cfg.rhosum_nstep > 0;
+    return multi() && overlap && (blk || use_row2()) && (force_mode & M_TAIT) != 0 &&
+           cfg.rhosum_nstep > 0;
   }
   // interior rows (no ghost in the list) and boundary rows, each in row order; on the block
   // path interior and boundary BLOCKS (no ghost in the union, k_blk_interior)
@@ -1897,7 +1743,7 @@ struct sph_engine {
     if (n)
       hipLaunchKernelGGL(k_row_ghost_flags, dim3((unsigned)(((long)n * 8 + 255) / 256)),
                          dim3(256), 0, s, n, nlocal, strided ? nullptr : off.p,
-                         strided ? list_stride : 0, ccnt.p, nbr.p, list_perm_g, list_perm_pi,
+                         strided ? list_stride : 0, ccnt.p, nbr.p, list_perm_g,
                          (strided && list_tbits) ? 1 : 0, fl_in.p, fl_bd.p);
     n_in = select_flagged(fl_in.p, n, rows_in);
     n_bd = select_flagged(fl_bd.p, n, rows_bd);
@@ -2037,9 +1883,7 @@ struct sph_engine {
       b.rcnt = ccnt.p;
     }
     b.lp = row2_lp();
-    b.pi = row2_pi();
-    b.iv = strided && list_perm_g > 0 && list_perm_g == row2_iv_g() &&
-           list_perm_pi == (b.pi ? 1 : 0);
+    b.iv = strided && list_perm_g > 0 && list_perm_g == row2_iv_g();
     b.exp = row2_exp();
     b.tbits = strided && list_tbits;
     return b;
@@ -2055,22 +1899,13 @@ struct sph_engine {
       return;
     }
     const int nall = nlocal + nghost;
-    bool tight = false;
     if (do_rhosum) {
       {
         Scope t(this, T_RHO);
         if (blk) {
           blk_rhosum(nt1(), s, blk_args(), xf.p, ty.p, vr.p, dc);
         } else if (use_row2()) {
-          Row2Args b = row2_args();
-          if (strided && row2_lp() && tight_on() && force_mode && !setup) {
-            tnbr.reserve((size_t)list_span());
-            tcnt.reserve(nlocal > 0 ? nlocal : 1);
-            b.tnbr = tnbr.p;
-            b.tcnt = tcnt.p;
-            tight = true;
-          }
-          row2_rhosum(nt1(), s, b);
+          row2_rhosum(nt1(), s, row2_args());
         } else {
           RhoArgs ra{nlocal, nullptr, off.p, nbr.p, xf.p, ty.p, vr.p, nullptr, dc};
           launch_rhosum(cfg.dim, true, nt1(), s, ra);
@@ -2094,13 +1929,7 @@ struct sph_engine {
       blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args());
     } else if (force_mode && use_row2()) {
       Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);
-      Row2Args b = row2_args();
-      if (tight) {  // this step's in-cut list from the rhosum pass (same strided rows)
-        b.a.nbr = tnbr.p;
-        b.rcnt = tcnt.p;
-        b.iv = false;
-      }
-      row2_force(nt1(), cfg.tait_visc, force_mode, s, b);
+      row2_force(nt1(), cfg.tait_visc, force_mode, s, row2_args());
     } else if (force_mode) {
       Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);
       ForceArgs a{};
@@ -2737,9 +2566,6 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
     // of 128 pair evaluations), valid while no atom has moved skin/32 since the build
     e->inner_margin = SPH_INNER_FRAC * cfg->skin;
     e->cutneighmax = coef_cutneigh(c, nt, cutmax.data(), cfg->skin, e->inner_margin);
-    for (int k = 0; k < NT2; k++)  // tight-list test: the largest force-style cutoff
-      c.fcutsq[k] = std::max((e->force_mode & M_TAIT) ? c.tait[k].cutsq : 0.0,
-                             (e->force_mode & M_HEAT) ? c.heat[k].cutsq : 0.0);
     SPH_REQUIRE(e->cutneighmax > 0.0, SPH_HIP_EINVAL, "no pair style enabled / zero cutoff");
     e->cutghost = e->cutneighmax;  // CommBrick::setup: cutghost = cutneighmax (:166)
     if (pgn > 1) {
@@ -2826,8 +2652,8 @@ int sph_engine_destroy(sph_engine *e) {
   e->red_out.release();
   for (auto *b : {&e->ty, &e->ty2, &e->tag, &e->tag2, &e->gowner, &e->gimg, &e->sel, &e->nsel,
                   &e->bidx, &e->bidx2, &e->cnt, &e->off, &e->nbr, &e->mx,
-                  &e->ccnt, &e->pcnt, &e->qbeg, &e->tb, &e->xpos, &e->sel2, &e->rows_in, &e->rows_bd, &e->tnbr,
-                  &e->tcnt, &e->ulist, &e->ucnt, &e->kcnt, &e->uilist, &e->uicnt})
+                  &e->ccnt, &e->qbeg, &e->tb, &e->xpos, &e->sel2, &e->rows_in, &e->rows_bd,
+                  &e->ulist, &e->ucnt, &e->kcnt, &e->uilist, &e->uicnt})
     b->release();
   for (auto *b : {&e->bkey, &e->bkey2}) b->release();
   for (auto *b : {&e->flags, &e->tmp, &e->cbs, &e->cbr, &e->flag2, &e->fl_in, &e->fl_bd}) b->release();

@@ -230,31 +230,6 @@ static __global__ void k_pbc(int n, Box b, double4 *__restrict__ xf, double4 *__
 }
 
 // ---- borders (one process: the left/right neighbor is this rank itself) -------------
-static __global__ void k_slab_flags(int n, int dim, double lo, double hi,
-                                    const double4 *__restrict__ xf,
-                                    unsigned char *__restrict__ flag) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const double4 x = xf[i];
-  const double c = dim == 0 ? x.x : (dim == 1 ? x.y : x.z);
-  flag[i] = (c >= lo && c <= hi) ? 1 : 0;
-}
-
-// k_slab_flags over [0, *n) of a launch sized for an upper bound (the count on the device)
-static __global__ void k_slab_flags_dev(int nmax, const int *__restrict__ n, int dim, double lo,
-                                        double hi, const double4 *__restrict__ xf,
-                                        unsigned char *__restrict__ flag) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nmax) return;
-  unsigned char f = 0;
-  if (i < *n) {
-    const double4 x = xf[i];
-    const double c = dim == 0 ? x.x : (dim == 1 ? x.y : x.z);
-    f = (c >= lo && c <= hi) ? 1 : 0;
-  }
-  flag[i] = f;
-}
-
 // image packed as 3 x 8-bit signed fields
 __host__ __device__ __forceinline__ int img_get(int img, int k) {
   return (int)(signed char)((img >> (8 * k)) & 0xff);
@@ -264,93 +239,13 @@ __host__ __device__ __forceinline__ int img_add(int img, int k, int d) {
   return (img & ~(0xff << (8 * k))) | ((v & 0xff) << (8 * k));
 }
 // a ghost's position from its owner's: + image * prd in each shifted dimension (k_forward's
-// arithmetic, shared with the block passes that read a ghost through its owner, BlkGhosts)
+// arithmetic)
 __device__ __forceinline__ double4 img_shift(double4 x, int img, const double *prd) {
   const int ix = img_get(img, 0), iy = img_get(img, 1), iz = img_get(img, 2);
   if (ix) x.x = x.x + ix * prd[0];
   if (iy) x.y = x.y + iy * prd[1];
   if (iz) x.z = x.z + iz * prd[2];
   return x;
-}
-
-// append the selected atoms as ghosts shifted by `shift` along `dim`
-// (comm_brick.cpp:820-860 -> atom_vec_meso.cpp:422-480 pack/unpack_border)
-static __global__ void k_append_ghosts(int nsel, const int *__restrict__ sel, int nlocal,
-                                       int nall, int dim, int pbc, double shift,
-                                       double4 *__restrict__ xf, double4 *__restrict__ vr,
-                                       double *__restrict__ en, int *__restrict__ ty,
-                                       int *__restrict__ gowner, int *__restrict__ gimg) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= nsel) return;
-  const int s = sel[k];
-  const int g = nall + k;
-  double4 x = xf[s];
-  if (dim == 0) x.x = x.x + shift;
-  else if (dim == 1) x.y = x.y + shift;
-  else x.z = x.z + shift;
-  xf[g] = x;
-  vr[g] = vr[s];
-  en[g] = en[s];
-  ty[g] = ty[s];
-  int own, img;
-  if (s < nlocal) {
-    own = s;
-    img = 0;
-  } else {
-    own = gowner[s - nlocal];
-    img = gimg[s - nlocal];
-  }
-  gowner[g - nlocal] = own;
-  gimg[g - nlocal] = img_add(img, dim, pbc);
-}
-
-// k_append_ghosts with the swap's counts on the device (no host round trip per swap):
-// *nsel atoms sel[] appended at nall = nalls[0]; nalls[1] <- the new nall.  A swap that would
-// pass `cap` atoms appends what fits and raises *ovf (the host redoes the borders with more
-// room).  Also the swap's sendlist (gsrc, if given) and the multiphase fields (vel, rm, cv,
-// cg, if given; atom_vec_meso_multiphase.cpp pack/unpack_border).
-static __global__ void k_append_ghosts_dev(
-    int gmax, const int *__restrict__ nsel, const int *__restrict__ sel, int nlocal,
-    int *__restrict__ nalls, int cap, int dim, int pbc, double shift, double4 *__restrict__ xf,
-    double4 *__restrict__ vr, double *__restrict__ en, int *__restrict__ ty,
-    int *__restrict__ gowner, int *__restrict__ gimg, int *__restrict__ gsrc,
-    double4 *__restrict__ vel, double *__restrict__ rm, double *__restrict__ cv,
-    double4 *__restrict__ cg, int *__restrict__ ovf) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ns = *nsel, nall = nalls[0];
-  if (k == 0) {
-    nalls[1] = min(nall + ns, cap);
-    if (nall + ns > cap) *ovf = 1;
-  }
-  if (k >= gmax || k >= ns || nall + k >= cap) return;
-  const int s = sel[k];
-  const int g = nall + k;
-  double4 x = xf[s];
-  if (dim == 0) x.x = x.x + shift;
-  else if (dim == 1) x.y = x.y + shift;
-  else x.z = x.z + shift;
-  xf[g] = x;
-  vr[g] = vr[s];
-  en[g] = en[s];
-  ty[g] = ty[s];
-  int own, img;
-  if (s < nlocal) {
-    own = s;
-    img = 0;
-  } else {
-    own = gowner[s - nlocal];
-    img = gimg[s - nlocal];
-  }
-  gowner[g - nlocal] = own;
-  gimg[g - nlocal] = img_add(img, dim, pbc);
-  if (gsrc) gsrc[g - nlocal] = s;
-  if (vel) {
-    const double4 v = vel[s], c = cg[s];
-    vel[g] = make_double4(v.x, v.y, v.z, vel[g].w);
-    rm[g] = rm[s];
-    cv[g] = cv[s];
-    cg[g] = make_double4(c.x, c.y, c.z, 0.0);
-  }
 }
 
 // ---- one brick's borders, one dimension in three launches ---------------------------------
@@ -360,7 +255,9 @@ static __global__ void k_append_ghosts_dev(
 // hi1], -prd) after them, each in scan order.  k_brd_count: per block of BRD_CH atoms the
 // two swaps' counts; k_brd_scan (one block): their exclusive prefixes and the new atom
 // counts nalls[1] = n + T0, nalls[2] = n + T0 + T1; k_brd_scatter: the ghosts, in scan
-// order (a block-wide prefix per swap), as k_append_ghosts_dev writes them.
+// order (a block-wide prefix per swap): position shifted, owner and image composed
+// (comm_brick.cpp:820-860 -> atom_vec_meso.cpp:422-480 pack/unpack_border), the swap's
+// sendlist (gsrc) and the multiphase fields (atom_vec_meso_multiphase.cpp) where given.
 constexpr int BRD_T = 256, BRD_IT = 4, BRD_CH = BRD_T * BRD_IT, BRD_W = BRD_T / 64;
 __device__ __forceinline__ double brd_coord(const double4 &x, int d) {
   return d == 0 ? x.x : (d == 1 ? x.y : x.z);
@@ -760,8 +657,8 @@ k_neigh3(int nlocal, QBins q, int dim, const double4 *__restrict__ xf,
          const int *__restrict__ ty, const double4 *__restrict__ xb,
          const int *__restrict__ tb, const int *__restrict__ beg,
          const Coefs *__restrict__ cf, int *__restrict__ cnt, const int *__restrict__ off,
-         int *__restrict__ nbr, int stride, int *__restrict__ ovf, int perm_g, int perm_pi,
-         int tbits, const MpCoefs *__restrict__ mc = nullptr,
+         int *__restrict__ nbr, int stride, int *__restrict__ ovf, int perm_g, int tbits,
+         const MpCoefs *__restrict__ mc = nullptr,
          const double *__restrict__ rm = nullptr, double *__restrict__ rho = nullptr) {
   constexpr int R = 2, NB = (2 * R + 1) * (2 * R + 1), GR = 256 / G, KB = (NB + G - 1) / G;
   static_assert(!RHO || FILL, "the rhosum terms ride on the fill passes");
@@ -876,7 +773,7 @@ k_neigh3(int nlocal, QBins q, int dim, const double4 *__restrict__ xf,
             ent |= (tj[u] - 1) << 28;
             if (half_keep(i, j, nlocal, xi, xj[u])) ent |= (int)0x80000000u;
           }
-          row[perm_g > 0 ? tpos(qq, perm_g, perm_pi) : qq] = ent;
+          row[perm_g > 0 ? tpos(qq, perm_g) : qq] = ent;
         }
         pos += __popcll(m);
       } else {
@@ -994,7 +891,7 @@ static __global__ void k_add_gravity(int n, StepConst sc, double gx, double gy, 
 static __global__ void __launch_bounds__(256)
 k_row_ghost_flags(int n, int nlocal, const int *__restrict__ off, int stride,
                   const int *__restrict__ rcnt, const int *__restrict__ nbr, int perm_g,
-                  int perm_pi, int tbits, unsigned char *__restrict__ in,
+                  int tbits, unsigned char *__restrict__ in,
                   unsigned char *__restrict__ bd) {
   constexpr int G = 8;
   const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) / G);
@@ -1007,7 +904,7 @@ k_row_ghost_flags(int n, int nlocal, const int *__restrict__ off, int stride,
   }
   bool ghost = false;
   for (int e = lane; e < cnt; e += G) {
-    const int q = (stride > 0 && perm_g > 0) ? tpos(e, perm_g, perm_pi) : e;
+    const int q = (stride > 0 && perm_g > 0) ? tpos(e, perm_g) : e;
     const int j = nbr[beg + q];
     ghost |= (tbits ? (j & SPH_TBIT_MASK) : j) >= nlocal;
   }

@@ -286,22 +286,22 @@ int sph_hip_build_list(sph_hip_ctx *c, int kind, int64_t key, const double *cutn
   const dim3 grid(grid_for_rows(nlocal, G)), block(256);
   const bool nt1 = nt == 1;
   DBuf<int> &foff = c->loff, &fnbr = c->lnbr;
-#define SPH_N3L(F, T, OFF, NBR)                                                                  \
+#define SPH_NGHL(F, T, OFF, NBR)                                                                 \
   hipLaunchKernelGGL((k_neigh3<G, 4, F, T>), grid, block, 0, c->stream, nlocal, q, c->dim,        \
                      (const double4 *)c->xf.p, (const int *)c->ty.p, (const double4 *)c->xb.p,    \
                      (const int *)c->tb.p, (const int *)c->qbeg.p, (const Coefs *)c->dc,         \
-                     (F ? (int *)nullptr : c->lcnt.p), OFF, NBR, 0, c->lbad.p, 0, 0, 0)
-  if (nt1) SPH_N3L(false, true, (const int *)nullptr, (int *)nullptr);
-  else SPH_N3L(false, false, (const int *)nullptr, (int *)nullptr);
+                     (F ? (int *)nullptr : c->lcnt.p), OFF, NBR, 0, c->lbad.p, 0, 0)
+  if (nt1) SPH_NGHL(false, true, (const int *)nullptr, (int *)nullptr);
+  else SPH_NGHL(false, false, (const int *)nullptr, (int *)nullptr);
   const long long ftot = scan_counts(c, c->lcnt.p, nlocal, foff);
   SPH_REQUIRE(ftot >= 0 && ftot < 0x7fffffffll, SPH_HIP_EOVERFLOW,
               "sph_hip_build_list: %lld list entries", ftot);
   fnbr.reserve(ftot > 0 ? ftot : 1);
   if (ftot) {
-    if (nt1) SPH_N3L(true, true, (const int *)foff.p, fnbr.p);
-    else SPH_N3L(true, false, (const int *)foff.p, fnbr.p);
+    if (nt1) SPH_NGHL(true, true, (const int *)foff.p, fnbr.p);
+    else SPH_NGHL(true, false, (const int *)foff.p, fnbr.p);
   }
-#undef SPH_N3L
+#undef SPH_NGHL
   if (kind == SPH_LIST_FULL) {
     std::swap(c->off, foff);
     std::swap(c->nbr, fnbr);

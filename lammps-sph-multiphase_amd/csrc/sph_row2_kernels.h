@@ -160,11 +160,11 @@ __device__ __forceinline__ unsigned nbytes(int n) {
 }
 
 // A lane's U neighbor indices of the chunk starting at list entry k0 (row entries
-// [beg, end)): entries k0 + el + u*G, el = the lane's entry slot (entry_slot) -- with IV
+// [beg, end)): entries k0 + lane + u*G -- with IV
 // from a chunk-transposed list, where they sit contiguously at k0 + 4*lane (one 16-B
 // load; U = 4; k0 16-B aligned).
 template <int G, int U, bool IV>
-__device__ __forceinline__ void chunk_idx(Rsrc rn, int k0, int lane, int el, int (&j)[U]) {
+__device__ __forceinline__ void chunk_idx(Rsrc rn, int k0, int lane, int (&j)[U]) {
   if (IV) {
     static_assert(!IV || U == 4, "index vectors hold 4 entries");
     const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rn, (unsigned)(k0 + 4 * lane) * 4u, 0,
@@ -175,49 +175,31 @@ __device__ __forceinline__ void chunk_idx(Rsrc rn, int k0, int lane, int el, int
     j[3] = (int)v.w;
   } else {
 #pragma unroll
-    for (int u = 0; u < U; u++) j[u] = ld_i32(rn, (unsigned)(k0 + el + u * G) * 4u);
+    for (int u = 0; u < U; u++) j[u] = ld_i32(rn, (unsigned)(k0 + lane + u * G) * 4u);
   }
 }
 template <int G, int U, bool IV>
-__device__ __forceinline__ int chunk_pos(int k0, int el, int u) {
-  return k0 + el + u * G;
+__device__ __forceinline__ int chunk_pos(int k0, int lane, int u) {
+  return k0 + lane + u * G;
 }
 
-// TIGHT (strided list, LP): also write this step's in-cut neighbors -- rsq inside the
-// force styles' cutoff (fcutsq), the only pairs the force pass can use, positions being
-// fixed between the two passes -- as a compacted "tight" list: row rr at tnbr + rr*stride,
-// tcnt[rr] entries.  The group compacts its hits through LDS and stores them 16 B at a
-// time (a quarter of the store instructions of per-lane 4-B stores, which cost the TA as
-// much as gathers); the force pass then walks ~25% fewer chunks.
-template <int G, int U, bool NT1, bool LP, bool IV, bool TIGHT>
+template <int G, int U, bool NT1, bool LP, bool IV>
 __global__ void __launch_bounds__(256)
 k_row2_rhosum(int n, int nall, int ntot, const int *__restrict__ off, int stride,
               const int *__restrict__ rcnt,
               const int *__restrict__ nbr, double4 *__restrict__ xf,
               const int *__restrict__ ty, double4 *__restrict__ vr,
-              const Coefs *__restrict__ cf, int *__restrict__ tnbr, int *__restrict__ tcnt,
-              int pi, const int *__restrict__ rows, int tbits) {
-  static_assert(!TIGHT || LP, "the tight-list compaction needs wave-uniform trip counts");
+              const Coefs *__restrict__ cf, const int *__restrict__ rows, int tbits) {
   __shared__ RhoPair s_c[NT1 ? 1 : NT2];
-  __shared__ double s_fc[(NT1 || !TIGHT) ? 1 : NT2];
-  // a group's buffer holds up to 3 carried entries + one chunk's G*U hits, rounded up to
-  // whole 16-B stores (G*U = 64 at tile 2 would overflow a 64-entry row)
-  constexpr int TQ = TIGHT ? (G * U + 3 + 3) / 4 * 4 : 4;
-  static_assert(!TIGHT || TQ >= G * U + 3, "tight-list buffer too small");
-  __shared__ __attribute__((aligned(16))) int s_tq[TIGHT ? 256 / G : 1][TQ];
   const int nt1 = cf->ntypes + 1;
   if (!NT1) {
-    for (int t = threadIdx.x; t < nt1 * nt1; t += blockDim.x) {
-      s_c[t] = cf->rho[t];
-      if (TIGHT) s_fc[t] = cf->fcutsq[t];
-    }
+    for (int t = threadIdx.x; t < nt1 * nt1; t += blockDim.x) s_c[t] = cf->rho[t];
     __syncthreads();
   }
   // rows != nullptr: the launch covers the n rows rows[0..n) (an interior / boundary
   // subset, see sph_engine overlap), else rows 0..n-1
   const int idx = (int)((xcd_block() * blockDim.x + threadIdx.x) / G);
   const int lane = threadIdx.x & (G - 1);
-  const int el = entry_slot<G>(lane, pi);
   // LP: lanes of rows past n stay in the loop (masked) so every DPP partner is active
   if (!LP && idx >= n) return;
   const bool live = idx < n;
@@ -234,23 +216,16 @@ k_row2_rhosum(int n, int nall, int ntot, const int *__restrict__ off, int stride
   // stride > 0: fixed-stride rows (row rr at rr*stride, rcnt[rr] entries), else CSR
   const int beg = stride > 0 ? rr * stride : off[rr];
   const int end = live ? (stride > 0 ? beg + rcnt[rr] : off[rr + 1]) : beg;
-  const double fc1 = (NT1 && TIGHT) ? cf->fcutsq[3] : 0.0;
-  const int gq = threadIdx.x / G, gbase = (threadIdx.x & 63) & ~(G - 1);
-  const unsigned long long gmask = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int *const trow = TIGHT ? tnbr + (size_t)rr * stride : nullptr;
-  int tq = 0, tw = 0;  // tight entries buffered in LDS / already stored (group-uniform)
   double acc = 0.0;
   int jn[U];
-  chunk_idx<G, U, IV>(rn, beg, lane, el, jn);
-  for (int k0 = beg; LP ? __any(chunk_pos<G, U, IV>(k0, el, 0) < end)
-                        : chunk_pos<G, U, IV>(k0, el, 0) < end;
+  chunk_idx<G, U, IV>(rn, beg, lane, jn);
+  for (int k0 = beg; LP ? __any(chunk_pos<G, U, IV>(k0, lane, 0) < end)
+                        : chunk_pos<G, U, IV>(k0, lane, 0) < end;
        k0 += G * U) {
     double3 xj[U];
-    int tj[U], jc[U];
+    int tj[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      jc[u] = jn[u];
       const unsigned o = ent_atom((unsigned)jn[u], tb);
       if (LP) {
         const unsigned jo = swap1(o);
@@ -262,7 +237,7 @@ k_row2_rhosum(int n, int nall, int ntot, const int *__restrict__ off, int stride
       }
       tj[u] = NT1 ? 1 : (tb ? ent_type((unsigned)jn[u], nt1 - 1) : ld_i32(rt, o * 4u));
     }
-    chunk_idx<G, U, IV>(rn, k0 + G * U, lane, el, jn);
+    chunk_idx<G, U, IV>(rn, k0 + G * U, lane, jn);
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const double dx = xi.x - xj[u].x, dy = xi.y - xj[u].y, dz = xi.z - xj[u].z;
@@ -271,33 +246,11 @@ k_row2_rhosum(int n, int nall, int ntot, const int *__restrict__ off, int stride
       double wf = 1.0 - rsq * c.ihsq;
       wf = wf * wf;
       wf = wf * wf;
-      const bool in = chunk_pos<G, U, IV>(k0, el, u) < end;
+      const bool in = chunk_pos<G, U, IV>(k0, lane, u) < end;
       acc += (in && rsq < c.cutsq) ? c.mK * wf : 0.0;
-      if (TIGHT) {
-        const bool hit = in && rsq < (NT1 ? fc1 : s_fc[it * nt1 + tj[u]]);
-        const unsigned long long m = (__ballot(hit) >> gbase) & gmask;
-        if (hit) s_tq[gq][tq + __popcll(m & below)] = jc[u];
-        tq += __popcll(m);
-      }
-    }
-    if (TIGHT) {  // store the complete 16-B groups, keep the remainder (< 4) buffered
-      // (a group's lanes are one wave: its LDS accesses complete in program order, and
-      // the compiler keeps may-aliasing LDS accesses in order, so no barrier is needed)
-      const int nfull = tq & ~3, rem = tq - nfull;
-      for (int k = lane; 4 * k < nfull; k += G)
-        *reinterpret_cast<int4 *>(trow + tw + 4 * k) = *reinterpret_cast<const int4 *>(&s_tq[gq][4 * k]);
-      const int carry = lane < rem ? s_tq[gq][nfull + lane] : 0;
-      if (lane < rem) s_tq[gq][lane] = carry;
-      tw += nfull;
-      tq = rem;
     }
   }
   acc = group_sum<G>(acc);
-  if (TIGHT && live && lane == 0) {
-    if (tq > 0)
-      *reinterpret_cast<int4 *>(trow + tw) = *reinterpret_cast<const int4 *>(&s_tq[gq][0]);
-    tcnt[row] = tw + tq;
-  }
   if (lane == 0 && live) {
     const double rho = ((cf->rho_keep >> it) & 1) ? vr[row].w : cf->self_rho[it] + acc;
     vr[row].w = rho;
@@ -313,7 +266,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
              const double4 *__restrict__ vr, const int *__restrict__ ty,
              const double *__restrict__ en, const Coefs *__restrict__ cf,
              double4 *__restrict__ fo, double *__restrict__ de, double gx, double gy,
-             double gz, int pi, const int *__restrict__ rows, int tbits) {
+             double gz, const int *__restrict__ rows, int tbits) {
   constexpr bool TAIT = (MODE & M_TAIT) != 0;
   constexpr bool HEAT = (MODE & M_HEAT) != 0;
   __shared__ TaitPair s_t[(TAIT && !NT1) ? NT2 : 1];
@@ -328,7 +281,6 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
   }
   const int idx = (int)((xcd_block() * blockDim.x + threadIdx.x) / G);
   const int lane = threadIdx.x & (G - 1);
-  const int el = entry_slot<G>(lane, pi);
   if (!LP && idx >= n) return;
   const bool live = idx < n;
   const bool odd = (threadIdx.x & 1) != 0;
@@ -355,9 +307,9 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
   const int end = live ? (stride > 0 ? beg + rcnt[rr] : off[rr + 1]) : beg;
   double fx = 0.0, fy = 0.0, fz = 0.0, drho = 0.0, dE = 0.0;
   int jn[U];
-  chunk_idx<G, U, IV>(rn, beg, lane, el, jn);
-  for (int k0 = beg; LP ? __any(chunk_pos<G, U, IV>(k0, el, 0) < end)
-                        : chunk_pos<G, U, IV>(k0, el, 0) < end;
+  chunk_idx<G, U, IV>(rn, beg, lane, jn);
+  for (int k0 = beg; LP ? __any(chunk_pos<G, U, IV>(k0, lane, 0) < end)
+                        : chunk_pos<G, U, IV>(k0, lane, 0) < end;
        k0 += G * U) {
     double4 xj[U], vj[U];
     double ej[U];
@@ -381,7 +333,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
       ej[u] = HEAT ? ld_d1(re, o * 8u) : 0.0;
       tj[u] = NT1 ? 1 : (tb ? ent_type((unsigned)jn[u], nt1 - 1) : ld_i32(rt, o * 4u));
     }
-    chunk_idx<G, U, IV>(rn, k0 + G * U, lane, el, jn);
+    chunk_idx<G, U, IV>(rn, k0 + G * U, lane, jn);
 #pragma unroll
     for (int u = 0; u < U; u++) {
       if (EXP == 1) {
@@ -394,7 +346,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
       const double dx = xi.x - xj[u].x, dy = xi.y - xj[u].y, dz = xi.z - xj[u].z;
       const double rsq = dx * dx + dy * dy + dz * dz;
       const int pidx = NT1 ? 3 : it * nt1 + tj[u];
-      const bool ok = chunk_pos<G, U, IV>(k0, el, u) < end;
+      const bool ok = chunk_pos<G, U, IV>(k0, lane, u) < end;
       const double r = sqrt1(rsq);
       if (TAIT) {
         const TaitPair c = NT1 ? t1 : s_t[pidx];
@@ -459,11 +411,9 @@ struct Row2Args {
   int nall, ntot;
   bool lp;   // lane-pair gathers
   bool iv;   // index vectors
-  bool pi;   // pair-interleaved entry slots (entry_slot)
   int exp;   // study variants (SPH_EXP), 0 in production
   int stride = 0;                 // > 0: fixed-stride rows with counts rcnt (else a.off CSR)
   const int *rcnt = nullptr;
-  int *tnbr = nullptr, *tcnt = nullptr;  // rhosum: write the tight list here (strided, LP)
   const int *rows = nullptr;             // a.n rows listed here instead of rows 0..a.n-1
   bool tbits = false;                    // typed list entries (k_neigh3 tbits)
 };
@@ -473,24 +423,19 @@ inline bool row2_fits(long nall, long ntot) {
   return ntot * 4L < 0x7fffffffL && nall * 32L < 0x7fffffffL;
 }
 
-template <int G, int U, bool LP, bool IV, bool TIGHT>
-inline void row2_rhosum_kt(bool nt1, hipStream_t s, const Row2Args &b) {
+template <int G, int U, bool LP, bool IV>
+inline void row2_rhosum_k(bool nt1, hipStream_t s, const Row2Args &b) {
   const RowArgs &a = b.a;
   const int grid = (int)(((long long)a.n * G + 255) / 256);
   if (grid == 0) return;
   if (nt1)
-    hipLaunchKernelGGL((k_row2_rhosum<G, U, true, LP, IV, TIGHT>), dim3(grid), dim3(256), 0, s,
-                       a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr,
-                       a.cf, b.tnbr, b.tcnt, b.pi ? 1 : 0, b.rows, b.tbits ? 1 : 0);
+    hipLaunchKernelGGL((k_row2_rhosum<G, U, true, LP, IV>), dim3(grid), dim3(256), 0, s, a.n,
+                       b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr, a.cf,
+                       b.rows, b.tbits ? 1 : 0);
   else
-    hipLaunchKernelGGL((k_row2_rhosum<G, U, false, LP, IV, TIGHT>), dim3(grid), dim3(256), 0, s,
-                       a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr,
-                       a.cf, b.tnbr, b.tcnt, b.pi ? 1 : 0, b.rows, b.tbits ? 1 : 0);
-}
-template <int G, int U, bool LP, bool IV>
-inline void row2_rhosum_k(bool nt1, hipStream_t s, const Row2Args &b) {
-  if (LP && b.tnbr) row2_rhosum_kt<G, U, LP, IV, LP>(nt1, s, b);
-  else row2_rhosum_kt<G, U, LP, IV, false>(nt1, s, b);
+    hipLaunchKernelGGL((k_row2_rhosum<G, U, false, LP, IV>), dim3(grid), dim3(256), 0, s, a.n,
+                       b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr, a.cf,
+                       b.rows, b.tbits ? 1 : 0);
 }
 
 template <int G, int U>
@@ -512,8 +457,7 @@ inline void row2_force_t(hipStream_t s, const Row2Args &b) {
   if (grid == 0) return;
   hipLaunchKernelGGL((k_row2_force<G, U, VISC, MODE, NT1, LP, IV, EXP>), dim3(grid), dim3(256),
                      0, s, a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.vr,
-                     a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy, a.gz, b.pi ? 1 : 0, b.rows,
-                     b.tbits ? 1 : 0);
+                     a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy, a.gz, b.rows, b.tbits ? 1 : 0);
 }
 
 template <int G, int U, bool NT1, bool LP, bool IV>

@@ -266,6 +266,7 @@ def test_no_viscosity_c2(gpu, sph_amd):
     ref.run(12)
     eng = engine_for(sph_amd, s, ph)
     eng.setup()
+    assert eng.stats()["staged"] == 1
     eng.run(12)
     assert np.array_equal(eng.neighbor_counts(), ref.numneigh_full())
     compare(eng, ref, path=0)
