@@ -325,11 +325,26 @@ typedef struct {
   int inner_rows;              /* block path: inner rows were built at the last rebuild */
   int inner_live;              /* ... and the last step's passes walked them (no atom had moved
                                   past their margin since they were written) */
-  int flags;                   /* bit 0: the last rhosum/multiphase was summed inside the
-                                  list fill (C5: its time is in ms_neigh, not ms_rhosum) */
+  int flags;                   /* SPH_STAT_* bits.  Bit 0: the last rhosum/multiphase was summed
+                                  inside the list fill (C5: its time is in ms_neigh, not
+                                  ms_rhosum).  Bits 1-5 describe the last block build and are 0
+                                  when staged == 0 */
   int64_t inner_refresh;       /* refresh launches since create (inner rows derived again
                                   between rebuilds when an atom passed their margin) */
 } sph_engine_stats;
+
+/* sph_engine_stats.flags */
+#define SPH_STAT_RHO_FUSED (1 << 0)    /* rhosum/multiphase summed inside the list fill */
+#define SPH_STAT_BLK_R32 (1 << 1)      /* the block build used 32-row blocks (after the 64-row
+                                          shape's unions or candidates did not fit) */
+#define SPH_STAT_BLK_BIGIMG (1 << 2)   /* ... and the large candidate image (the bitmap build) */
+#define SPH_STAT_BLK_NOPRE (1 << 3)    /* the pair passes walk the slot rows chunk by chunk,
+                                          without the register preload: the slot-row stride is
+                                          past the preload's 256 entries */
+#define SPH_STAT_BLK_ROWRETRY (1 << 4) /* the build was repeated with a doubled slot-row stride
+                                          after a row outgrew it */
+#define SPH_STAT_BLK_IMGRETRY (1 << 5) /* the build was repeated after a block outgrew the small
+                                          candidate image */
 
 typedef struct sph_engine sph_engine;
 

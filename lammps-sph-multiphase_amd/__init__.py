@@ -811,6 +811,13 @@ class Engine:
         _chk(self.L.sph_engine_neighbor_counts(self.h, c))
         return c
 
+    # stats()["flags"] (SPH_STAT_* in include/sph_hip.h).  STAT_BLK_* describe the last block
+    # build (0 when staged == 0): 32-row blocks; the large candidate image; slot rows walked
+    # without the register preload (stride past 256 entries); the build repeated after a row
+    # outgrew the slot-row stride; ... after a block outgrew the small candidate image
+    STAT_RHO_FUSED, STAT_BLK_R32, STAT_BLK_BIGIMG = 1 << 0, 1 << 1, 1 << 2
+    STAT_BLK_NOPRE, STAT_BLK_ROWRETRY, STAT_BLK_IMGRETRY = 1 << 3, 1 << 4, 1 << 5
+
     def stats(self) -> dict:
         s = EngineStats()
         _chk(self.L.sph_engine_stats_get(self.h, C.byref(s)))

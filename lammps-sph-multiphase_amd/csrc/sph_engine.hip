@@ -289,6 +289,9 @@ struct sph_engine {
   DBuf<int> uilist, uicnt;
   bool blk_ksmall = false;  // k_blk_build with the small candidate image (BLK_SCAP_S)
   int blk_kover = 0;        // ... builds it overflowed
+  // what the last block build did (sph_engine_stats.flags, SPH_STAT_BLK_*); blk_retry: the
+  // repeats of the build_blk call under way (SPH_STAT_BLK_ROWRETRY | SPH_STAT_BLK_IMGRETRY)
+  int blk_flags = 0, blk_retry = 0;
   // ... and the inner rows of the build (k_blk_inner: pairs within cut + inner_margin), the
   // owned positions they were written at and the flag that retires them (sc.x0 / sc.moved)
   DBuf<unsigned short> snbi;
@@ -1471,6 +1474,7 @@ struct sph_engine {
     mx.reserve(10);
     ccnt.reserve(n + 1);
     if (blk_rowcap == 0) blk_rowcap = std::max(list_stride, nbr_maxrow + nbr_maxrow / 4 + 16);
+    blk_flags = blk_retry = 0;
     // the SPH_BLK shape, then 32-row blocks (smaller unions), then 32-row blocks with the
     // build's large candidate image, if the blocks do not fit
     const int first = blk_shape_env();
@@ -1488,7 +1492,11 @@ struct sph_engine {
     const int n = nlocal;
     const BlkShape sh = blk_shape(shape);
     const int chunk = sh.G * sh.U;
-    for (int attempt = 0; attempt < 3; attempt++) {
+    // repeats are counted per cause, so that one cause cannot spend the other's: the small
+    // candidate image overflows at most once (the repeat takes BLK_SCAP); the stride is tried
+    // at 1x, 2x and 4x the sized row (a third overflow doubles it once more for the next
+    // rebuild and this build goes to the row path)
+    for (int nrow = 0, nimg = 0; nrow < 3 && nimg < 2;) {
       blk_sstride = (std::max(blk_rowcap, 1) + chunk - 1) / chunk * chunk;
       snbr.reserve((size_t)n * blk_sstride + 2 * chunk);  // + the pair passes' prefetch pad
       const int nb = blk_blocks(n, sh.R);
@@ -1532,10 +1540,14 @@ struct sph_engine {
       if (hm[0] == (1 << 24)) {  // a block outgrew the small candidate image
         blk_ksmall = false;
         blk_kover++;
+        blk_retry |= SPH_STAT_BLK_IMGRETRY;
+        nimg++;
         continue;
       }
       if (hm[0] == (1 << 21)) {  // a row outgrew the slot-row stride
         blk_rowcap *= 2;
+        blk_retry |= SPH_STAT_BLK_ROWRETRY;
+        nrow++;
         continue;
       }
       if (hm[0] != 0) return 2;
@@ -1553,6 +1565,8 @@ struct sph_engine {
       // the CU's 160 KiB
       blk_sh = shape;
       blk_um = std::max(hm[1], 1);
+      blk_flags = (shape == 1 ? SPH_STAT_BLK_R32 : 0) | (big ? SPH_STAT_BLK_BIGIMG : 0) |
+                  (blk_args_pre(sh) ? 0 : SPH_STAT_BLK_NOPRE) | blk_retry;
       // the force pass's LDS image: sized to the union the passes stage (the inner one when
       // the build wrote it), for as many workgroups per CU as fit; larger unions are walked
       // in windows (k_blk_force)
@@ -1593,6 +1607,11 @@ struct sph_engine {
     else umf = std::min(m16, cap(2));
     if (blkumf > 0) umf = std::min(umf, std::max(16, blkumf / 16 * 16));
     return umf;
+  }
+  bool blk_args_pre(const BlkShape &sh) const {  // (BlkArgs::pre of the current stride)
+    BlkArgs k;
+    k.sstride = blk_sstride;
+    return k.pre(sh);
   }
   BlkArgs blk_args() const {
     BlkArgs k;
@@ -3197,7 +3216,8 @@ int sph_engine_stats_get(sph_engine *e, sph_engine_stats *st) {
     SPH_HIP_TRY(hipStreamSynchronize(e->s));
     st->inner_live = mv == 0 ? 1 : 0;
   }
-  st->flags = (e->rho_fused_step >= 0 && e->rho_fused_step == e->step) ? 1 : 0;
+  st->flags = (e->rho_fused_step >= 0 && e->rho_fused_step == e->step) ? SPH_STAT_RHO_FUSED : 0;
+  if (e->blk) st->flags |= e->blk_flags;
   st->inner_refresh = e->inner_refreshes;
   SPH_API_END
 }

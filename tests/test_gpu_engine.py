@@ -56,7 +56,9 @@ PATHS = [0, 1]   # 0 = block-staged LDS unions (production), 1 = row path (globa
 def test_setup_c2(gpu, sph_amd, sort, path, umf):
     """path 0 = block-staged passes (LDS unions, 16-bit slot rows built from the bins), 1 =
     the row path.  umf = 64 caps the force pass's LDS image at 64 records (sph_engine_tune
-    SPH_TUNE_BLKUMF), so nearly every block runs in the large-union launch; unsorted rows
+    SPH_TUNE_BLKUMF), so the build counts nearly every block as windowed (blk_nbig) -- setup
+    itself runs the block rhosum and the CSR setup force (setup_forces_full), not the windowed
+    force walk: test_gpu_block_paths.py steps such engines --; unsorted rows
     (sort 0) make blocks too wide for the build's candidate image, so the build takes its
     large-image variant."""
     s = c2_system(12)
