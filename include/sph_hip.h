@@ -328,7 +328,9 @@ typedef struct {
   int flags;                   /* SPH_STAT_* bits.  Bit 0: the last rhosum/multiphase was summed
                                   inside the list fill (C5: its time is in ms_neigh, not
                                   ms_rhosum).  Bits 1-5 describe the last block build and are 0
-                                  when staged == 0 */
+                                  when staged == 0.  Bits 6-9 (SPH_STAT_MP_*) name the gather
+                                  family of the last multiphase force pass and where the last
+                                  due rhosum was summed */
   int64_t inner_refresh;       /* refresh launches since create (inner rows derived again
                                   between rebuilds when an atom passed their margin) */
 } sph_engine_stats;
@@ -345,6 +347,16 @@ typedef struct {
                                           after a row outgrew it */
 #define SPH_STAT_BLK_IMGRETRY (1 << 5) /* the build was repeated after a block outgrew the small
                                           candidate image */
+/* multiphase engines: the gather family the last force pass launched (one of three; none when
+   taitwater, surfacetension and heatconduction are all off) ... */
+#define SPH_STAT_MP_W4 (1 << 6)        /* k_mp2_gather_w4: symmetric styles, every gamma 1 */
+#define SPH_STAT_MP_POW (1 << 7)       /* k_mp2_gather<POW>: symmetric styles, one gamma != 1 */
+#define SPH_STAT_MP_ROW (1 << 8)       /* k_mp_gather: unequal gammas, or a type pinned to Tc
+                                          against its own type */
+/* ... and whether the last rhosum/multiphase that was due was summed inside the list fill
+   (bit 0 says so for the current step only; this bit keeps the answer over the steps between
+   two due ones, rhosum_nstep > 1) */
+#define SPH_STAT_MP_RHO_LISTFILL (1 << 9)
 
 typedef struct sph_engine sph_engine;
 

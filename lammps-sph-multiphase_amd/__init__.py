@@ -817,6 +817,11 @@ class Engine:
     # outgrew the slot-row stride; ... after a block outgrew the small candidate image
     STAT_RHO_FUSED, STAT_BLK_R32, STAT_BLK_BIGIMG = 1 << 0, 1 << 1, 1 << 2
     STAT_BLK_NOPRE, STAT_BLK_ROWRETRY, STAT_BLK_IMGRETRY = 1 << 3, 1 << 4, 1 << 5
+    # STAT_MP_* (multiphase engines): the gather family of the last force pass -- W4
+    # (k_mp2_gather_w4: symmetric styles, every gamma 1), POW (k_mp2_gather: symmetric, one
+    # gamma != 1) or ROW (k_mp_gather: unequal gammas or a type pinned to Tc against itself)
+    # -- and whether the last due rhosum/multiphase was summed inside the list fill
+    STAT_MP_W4, STAT_MP_POW, STAT_MP_ROW, STAT_MP_RHO_LISTFILL = 1 << 6, 1 << 7, 1 << 8, 1 << 9
 
     def stats(self) -> dict:
         s = EngineStats()

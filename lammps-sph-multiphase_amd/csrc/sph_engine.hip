@@ -292,6 +292,9 @@ struct sph_engine {
   // what the last block build did (sph_engine_stats.flags, SPH_STAT_BLK_*); blk_retry: the
   // repeats of the build_blk call under way (SPH_STAT_BLK_ROWRETRY | SPH_STAT_BLK_IMGRETRY)
   int blk_flags = 0, blk_retry = 0;
+  // which gather family the last multiphase force pass launched, and whether the last due
+  // rhosum/multiphase came from the list fill (sph_engine_stats.flags, SPH_STAT_MP_*)
+  int mp_flags = 0;
   // ... and the inner rows of the build (k_blk_inner: pairs within cut + inner_margin), the
   // owned positions they were written at and the flag that retires them (sc.x0 / sc.moved)
   DBuf<unsigned short> snbi;
@@ -1369,6 +1372,10 @@ struct sph_engine {
     auto launch = [&](bool fill, int stride, int *dst = nullptr) {
       if (n == 0) return;
       const bool t = nt1();
+      // asymmetric multiphase styles (k_mp_gather): owned pairs take the half-list orientation
+      // of the reference's local order, i.e. by tag (k_neigh3 tg); the symmetric gathers
+      // never read an owned pair's orientation
+      const int *const tgp = (mp && !mp2_symmetric(hm)) ? tag.p : (const int *)nullptr;
       int *const cnt_out = (!fill || stride > 0) ? ccnt.p : (int *)nullptr;
       int *const rows = dst ? dst : nbr.p;
 #define SPH_NGHP(F, T, P)                                                                       \
@@ -1377,13 +1384,14 @@ struct sph_engine {
                      xb.p, tb.p, qbeg.p, dc, cnt_out,                                          \
                      (F && stride == 0) ? off.p : (const int *)nullptr,                        \
                      F ? rows : (int *)nullptr, stride, mx.p, stride > 0 ? list_perm_g : 0,    \
-                     mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0))
+                     mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0), (const MpCoefs *)nullptr,  \
+                     (const double *)nullptr, (double *)nullptr, tgp)
 #define SPH_NGHR(T)                                                                             \
   hipLaunchKernelGGL((k_neigh3<G, 4, true, T, true, true>), grid, block, 0, s, n, qb, cfg.dim,  \
                      xi_src,                                                                   \
                      ty.p, xb.p, tb.p, qbeg.p, dc, cnt_out,                                    \
                      stride == 0 ? off.p : (const int *)nullptr, rows, stride, mx.p, 0, 2,    \
-                     dm, rm.p, rho_tmp.p)
+                     dm, rm.p, rho_tmp.p, tgp)
       // (mp: xb packs the types, k_bin_copy tpack)
 #define SPH_NGH(F, T)                                                                           \
   do {                                                                                        \
@@ -2060,6 +2068,8 @@ struct sph_engine {
         a.rho = rho_tmp.p;
         if (rho_fused_step != step)  // (else the list fill of this step summed it)
           hipLaunchKernelGGL(k_mp2_rhosum<8>, mp_rows(n), dim3(256), 0, s, a);
+        mp_flags = (mp_flags & ~SPH_STAT_MP_RHO_LISTFILL) |
+                   (rho_fused_step == step ? SPH_STAT_MP_RHO_LISTFILL : 0);
         hipLaunchKernelGGL(k_mp_rho_store, dim3(blocks(n)), dim3(BLK), 0, s, n, rho_tmp.p, vr.p);
       }
       if (cdue) {
@@ -2117,6 +2127,8 @@ struct sph_engine {
     h.pS = recS.p;
     const int sel = (mpc.tait_on ? 1 : 0) | (mpc.st_on ? 2 : 0) | (mpc.heat_on ? 4 : 0);
     const bool g1 = mp2_gamma1(hm);
+    mp_flags = (mp_flags & SPH_STAT_MP_RHO_LISTFILL) |
+               (sel == 0 ? 0 : sym && g1 ? SPH_STAT_MP_W4 : sym ? SPH_STAT_MP_POW : SPH_STAT_MP_ROW);
     switch (sel) {
 #define SPH_MPG(k, T, S, H)                                                                   \
   case k:                                                                                     \
@@ -3218,6 +3230,7 @@ int sph_engine_stats_get(sph_engine *e, sph_engine_stats *st) {
   }
   st->flags = (e->rho_fused_step >= 0 && e->rho_fused_step == e->step) ? SPH_STAT_RHO_FUSED : 0;
   if (e->blk) st->flags |= e->blk_flags;
+  if (e->mp) st->flags |= e->mp_flags;
   st->inner_refresh = e->inner_refreshes;
   SPH_API_END
 }

@@ -659,7 +659,8 @@ k_neigh3(int nlocal, QBins q, int dim, const double4 *__restrict__ xf,
          const Coefs *__restrict__ cf, int *__restrict__ cnt, const int *__restrict__ off,
          int *__restrict__ nbr, int stride, int *__restrict__ ovf, int perm_g, int tbits,
          const MpCoefs *__restrict__ mc = nullptr,
-         const double *__restrict__ rm = nullptr, double *__restrict__ rho = nullptr) {
+         const double *__restrict__ rm = nullptr, double *__restrict__ rho = nullptr,
+         const int *__restrict__ tg = nullptr) {
   constexpr int R = 2, NB = (2 * R + 1) * (2 * R + 1), GR = 256 / G, KB = (NB + G - 1) / G;
   static_assert(!RHO || FILL, "the rhosum terms ride on the fill passes");
   __shared__ double s_cns[NT2];
@@ -728,6 +729,7 @@ k_neigh3(int nlocal, QBins q, int dim, const double4 *__restrict__ xf,
   // (TP: xb.w packs the type, k_bin_copy tpack)
   const double di = TP ? (double)(i | ((NT1 ? 0 : ty[i] - 1) << 28)) : (double)i;
   const int rrow = RHO ? (NT1 ? 1 : ty[i]) * nt1 : 0;
+  const int tgi = (FILL && tg) ? tg[i] : 0;
   double racc = 0.0;
   int n = 0;
   int *const row = FILL ? nbr + (stride > 0 ? (size_t)i * stride : (size_t)off[i]) : nullptr;
@@ -771,7 +773,12 @@ k_neigh3(int nlocal, QBins q, int dim, const double4 *__restrict__ xf,
           if (tbits == 1) ent |= (tj[u] - 1) << SPH_TBIT_SHIFT;
           if (tbits == 2) {  // (+ the type, MpArgs::typed)
             ent |= (tj[u] - 1) << 28;
-            if (half_keep(i, j, nlocal, xi, xj[u])) ent |= (int)0x80000000u;
+            // tg (asymmetric styles, k_mp_gather): an owned pair is the atom's that comes
+            // first in the reference's local order -- tag order, not the engine's spatially
+            // sorted rows; which of two owned atoms evaluates a pair shows only there
+            // (p_j with gamma[itype], the own-type Tc pin)
+            const bool mine = (tg && j < nlocal) ? tgi < tg[j] : half_keep(i, j, nlocal, xi, xj[u]);
+            if (mine) ent |= (int)0x80000000u;
           }
           row[perm_g > 0 ? tpos(qq, perm_g) : qq] = ent;
         }

@@ -648,14 +648,21 @@ SPREAD_ORDERS = (True, "rotate")  # rows reversed; rows rotated by half their le
 SPREAD_ULP_SEED = 4242
 
 
-def ulp_perturbed(sysm: "System", seed=SPREAD_ULP_SEED) -> "System":
-    """a copy of the system with x, v, rho, e each moved by one ulp, random sign"""
+def ulp_perturbed(sysm: "System", seed=SPREAD_ULP_SEED, planar=False) -> "System":
+    """a copy of the system with x, v, rho, e each moved by one ulp, random sign.  planar: a
+    2-D system keeps z = 0 and vz = 0 exactly (as fix enforce2d does) -- otherwise z moves to
+    +-5e-324, which leaves every distance alone but turns the half list's ghost ownership
+    (z, then y, then x above the row atom, neigh_derive.cpp:124-131) around for half the
+    owned-ghost pairs: a different evaluation, not a last-bit change of this one"""
     s = sysm.copy()
     rng = np.random.default_rng(seed)
     x0 = s.x.copy()
     for name in ("x", "v", "rho", "e"):
         a = getattr(s, name)
-        a += np.spacing(a) * rng.choice((-1.0, 1.0), size=a.shape)
+        d = np.spacing(a) * rng.choice((-1.0, 1.0), size=a.shape)
+        if planar and s.dim == 2 and a.ndim == 2:
+            d[:, 2] = 0.0
+        a += d
     for d in range(s.dim):  # (an atom moved out of the box keeps its coordinate)
         out = (s.x[:, d] < s.boxlo[d]) | (s.x[:, d] >= s.boxhi[d])
         s.x[out, d] = x0[out, d]
@@ -681,7 +688,9 @@ class _Spread:
     them, while any change in a term's last bits does: the reference's OWN sources built
     those ways move C5 colour-gradient / multiphase-force elements by up to ~1e-9 / ~1e-7
     relative (tools/fma_build_shift.py, profiles/r06/fma_build_shift.json), so the C5 bar is
-    16 x how far the reference moves between legitimate builds of itself."""
+    16 x how far the reference moves between legitimate builds of itself.  On jittered input
+    nothing cancels pairwise and those two are not needed: MpRefRun(spread="nobuild") does not
+    create them, and spread(k, builds=False) leaves them out of a run that has them."""
 
     def _init_spread(self, spread, make, make_ulp, build=False):
         self.alts = []
@@ -732,14 +741,17 @@ class _Spread:
             out = r if out is None else max(out, r)
         return out
 
-    def spread(self, k):
-        """per-element spread of field k (None without shadow runs)"""
+    def spread(self, k, builds=True):
+        """per-element spread of field k (None without shadow runs); builds=False leaves the
+        build-variation shadows out: the reordering and one-ulp spread alone"""
         if not self.alts:
             return None
         want = np.asarray(self.field(k), dtype=np.float64)
         out = np.zeros_like(want)
         used = 0
         for a in self.alts:
+            if a.build and not builds:
+                continue
             # (a shadow whose fix phase_change took another decision -- a candidate's
             # temperature within its last bits of the threshold -- is left out)
             if a.s.n != self.s.n or not np.array_equal(a.s.type, self.s.type):
@@ -1216,8 +1228,9 @@ class MpRefRun(_Spread):
         self.rev = False
         self._init_spread(spread, lambda: MpRefRun(sysm, ph, cg=cg, procgrid=procgrid,
                                                    read_order=read_order),
-                          lambda: MpRefRun(ulp_perturbed(sysm), ph, cg=cg, procgrid=procgrid,
-                                           read_order=read_order), build=True)
+                          lambda: MpRefRun(ulp_perturbed(sysm, planar=spread == "nobuild"), ph,
+                                           cg=cg, procgrid=procgrid,
+                                           read_order=read_order), build=spread != "nobuild")
         self.ph = ph
         nt = sysm.ntypes
         self.cns, self.cutneighmax = cutneighsq(nt, ph.cutmax(nt), ph.skin)
