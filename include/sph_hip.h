@@ -357,6 +357,12 @@ typedef struct {
    (bit 0 says so for the current step only; this bit keeps the answer over the steps between
    two due ones, rhosum_nstep > 1) */
 #define SPH_STAT_MP_RHO_LISTFILL (1 << 9)
+/* the last build's bin copy / the last sort of the owned rows took the counting sort (and not
+   the radix sort: SPH_TUNE_CSORT 0, a key space too large for the atoms, or a segment past the
+   cap).  In flags on the block path and in multiphase engines; sph_engine_csort_paths gives
+   the two bits on every path */
+#define SPH_STAT_CSORT_BINS (1 << 10)
+#define SPH_STAT_CSORT_ROWS (1 << 11)
 
 typedef struct sph_engine sph_engine;
 
@@ -392,10 +398,15 @@ int sph_engine_comm_ipc(sph_engine *e, const char *name, int nranks, int rank, i
    rather than through the environment; before sph_engine_setup.
    SPH_TUNE_OVERLAP: bricks on the row path overlap interior rows' passes with the halo
    exchange (1) or not (0, default).  SPH_TUNE_BLKUMF: cap the block force pass's LDS image
-   at `value` records, blocks with larger unions going to its second launch (0 = auto). */
+   at `value` records, blocks with larger unions going to its second launch (0 = auto).
+   SPH_TUNE_CSORT: the rebuild orders bins and rows by counting sorts (1, default) or by the
+   radix sorts alone (0); 2 = counting, the bin copy as a pass of its own (measurement). */
 #define SPH_TUNE_OVERLAP 1
 #define SPH_TUNE_BLKUMF 2
+#define SPH_TUNE_CSORT 3
 int sph_engine_tune(sph_engine *e, int key, int value);
+/* SPH_STAT_CSORT_* of the last build, on every pair path */
+int sph_engine_csort_paths(sph_engine *e, int *mask);
 int sph_engine_set_tags(sph_engine *e, const int *tags);
 
 /* Owned particles of this rank (tag order is the caller's order; results are returned in

@@ -227,6 +227,7 @@ EXPORTS = {
     "sph_engine_comm_local": (_i, [_vp, _vp, _i]),
     "sph_engine_comm_ipc": (_i, [_vp, C.c_char_p, _i, _i, _i]),
     "sph_engine_tune": (_i, [_vp, _i, _i]),
+    "sph_engine_csort_paths": (_i, [_vp, C.POINTER(_i)]),
     "sph_engine_set_tags": (_i, [_vp, _ip]),
     "sph_engine_set_atoms": (_i, [_vp, _i, _dp, _dp, _ip, _dp, _vp, _vp]),
     "sph_engine_setup": (_i, [_vp]),
@@ -788,7 +789,8 @@ class Engine:
         buf = C.create_string_buffer(bytes(uid), 128)
         _chk(self.L.sph_engine_comm_init(self.h, buf, nranks, rank))
 
-    TUNE_OVERLAP, TUNE_BLKUMF = 1, 2
+    # TUNE_CSORT: 1 = the rebuild's counting sorts (default), 0 = the radix sorts alone
+    TUNE_OVERLAP, TUNE_BLKUMF, TUNE_CSORT = 1, 2, 3
 
     def tune(self, key: int, value: int):
         """sph_engine_tune: a schedule choice that does not change results (before setup)."""
@@ -822,6 +824,14 @@ class Engine:
     # gamma != 1) or ROW (k_mp_gather: unequal gammas or a type pinned to Tc against itself)
     # -- and whether the last due rhosum/multiphase was summed inside the list fill
     STAT_MP_W4, STAT_MP_POW, STAT_MP_ROW, STAT_MP_RHO_LISTFILL = 1 << 6, 1 << 7, 1 << 8, 1 << 9
+    # the last build's bin copy / the last row sort took the counting sort (in flags on the
+    # block path and in multiphase engines; csort_paths() on every path)
+    STAT_CSORT_BINS, STAT_CSORT_ROWS = 1 << 10, 1 << 11
+
+    def csort_paths(self) -> int:
+        m = _i(0)
+        _chk(self.L.sph_engine_csort_paths(self.h, C.byref(m)))
+        return m.value
 
     def stats(self) -> dict:
         s = EngineStats()

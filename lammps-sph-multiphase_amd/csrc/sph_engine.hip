@@ -270,6 +270,15 @@ struct sph_engine {
   DBuf<double4> xb;
   DBuf<unsigned> bkey, bkey2;
   DBuf<int> bidx, bidx2;
+  // counting sorts of bin_q (slot 0) and sort_owned (slot 1), cs_count(): the key counts,
+  // sort_owned's segment starts, the builds' long-segment words and their pinned host copies
+  DBuf<int> cs_cnt, cs_beg, cs_mx;
+  int *h_cs = nullptr;
+  hipEvent_t cs_ev[2] = {nullptr, nullptr};
+  bool cs_pending[2] = {false, false};
+  int cs_prev[2] = {-1, -1};  // the last build's longest segment above CS_CAP / 2 (0: none; -1: unknown)
+  int csort = 1;              // SPH_TUNE_CSORT: 0 = radix sorts only, 2 = bin copy not fused
+  int cs_flags = 0;           // SPH_STAT_CSORT_*: what the last bin copy / row sort took
   // neighbor list
   DBuf<int> cnt, off, nbr;
   int64_t nbr_total = 0;   // list entries (-1: strided list, counted on demand)
@@ -405,6 +414,57 @@ struct sph_engine {
   }
 
   // ------------------------------------------------------------------------------------
+  // Counting sort of xf[0, n) by the key of k_bin_keys (sph_engine_kernels.h, k_cs_*), first
+  // half: histogram (keys -> bkey, arrival numbers -> bkey2) and the exclusive scan of the
+  // K + 1 counts into beg.  w = 0 (bin_q) | 1 (sort_owned).  False = take the radix sort:
+  //  * SPH_TUNE_CSORT 0;
+  //  * a key space the atoms do not fill: counting while K <= CS_KFLOOR or K <= CS_KPERN * n,
+  //    never past CS_KMAX (the 30-bit curve keys of large boxes, a few atoms in a wide box:
+  //    clearing and scanning the counts would cost more than the radix passes);
+  //  * a segment longer than CS_CAP (k_cs_place reads a whole segment per element).
+  // The longest segment is known on the device after the histogram.  While the build before
+  // (of the same sort) saw none above CS_CAP / 2, this one goes on without waiting for its
+  // own word -- bin counts move by a few atoms between rebuilds -- and that word is read
+  // back behind the build for the next one.  The first build, and any build after one that
+  // came within a factor two of the cap, waits for the word (one stream synchronisation) and
+  // decides on its own count.  Whatever the segment lengths, the order is the exact one.
+  static constexpr int CS_KFLOOR = 1 << 16, CS_KPERN = 4, CS_KMAX = 1 << 24;
+  bool cs_count(int w, int n, long long K0, const Bins &b, int morton, int hdim,
+                DBuf<int> &begb) {
+    if (!csort || n < 1 || K0 < 1 || K0 > CS_KMAX) return false;
+    if (K0 > CS_KFLOOR && K0 > (long long)CS_KPERN * n) return false;
+    const int K = (int)K0;
+    begb.reserve((size_t)K + 1);
+    int *const beg = begb.p;
+    int prev = cs_prev[w];
+    if (cs_pending[w]) {
+      SPH_HIP_TRY(hipEventSynchronize(cs_ev[w]));
+      cs_pending[w] = false;
+      prev = h_cs[w];
+    }
+    if (!setup_done) prev = -1;
+    cs_cnt.reserve((size_t)K + 1);
+    cs_mx.reserve(2);
+    SPH_HIP_TRY(hipMemsetAsync(cs_cnt.p, 0, ((size_t)K + 1) * sizeof(int), s));
+    SPH_HIP_TRY(hipMemsetAsync(cs_mx.p + w, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_cs_hist, dim3(blocks(n)), dim3(BLK), 0, s, n, b, xf.p, bkey.p,
+                       (int *)bkey2.p, cs_cnt.p, K, cs_mx.p + w, morton, hdim);
+    SPH_HIP_TRY(hipMemcpyAsync(h_cs + w, cs_mx.p + w, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (prev != 0) {
+      SPH_HIP_TRY(hipStreamSynchronize(s));
+      cs_prev[w] = h_cs[w];
+      if (cs_prev[w] > CS_CAP) return false;
+    } else {
+      SPH_HIP_TRY(hipEventRecord(cs_ev[w], s));
+      cs_pending[w] = true;
+    }
+    size_t tb = 0;
+    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cs_cnt.p, beg, K + 1, s));
+    tmp_reserve(tb);
+    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cs_cnt.p, beg, K + 1, s));
+    return true;
+  }
+
   void sort_owned() {
     if (nlocal < 1) return;
     const int n = nlocal;
@@ -457,8 +517,7 @@ struct sph_engine {
     const int mx3 = std::max(kbn.nb[0], std::max(kbn.nb[1], kbn.nb[2]));
     while ((1 << cb) < mx3) cb++;
     const bool hil = mort && want_blk() && cb >= 2;
-    hipLaunchKernelGGL(k_bin_keys, dim3(blocks(n)), dim3(BLK), 0, s, n, 0, kbn, xf.p, bkey.p,
-                       bidx.p, hil ? cb + 1 : (mort ? 1 : 0), cfg.dim);
+    const int morton = hil ? cb + 1 : (mort ? 1 : 0);
     // key bits: dim (Hilbert) or 3 (Morton) x bits of the largest cell dimension, else
     // bits(nbins)
     int kb = 1;
@@ -467,10 +526,25 @@ struct sph_engine {
     } else {
       while ((1u << kb) < (unsigned)nbins && kb < 32) kb++;
     }
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
+    // the permutation bidx2: the counting sort over the 2^kb keys (k_cs_*: the order within a
+    // key by index, as the stable radix sort's), else the radix sort
+    cs_flags &= ~SPH_STAT_CSORT_ROWS;
+    if (cs_count(1, n, 1ll << kb, kbn, morton, cfg.dim, cs_beg)) {
+      hipLaunchKernelGGL(k_cs_scatter, dim3(blocks(n)), dim3(BLK), 0, s, n, bkey.p,
+                         (const int *)bkey2.p, cs_beg.p, bidx.p);
+      hipLaunchKernelGGL(k_cs_place<false>, dim3(blocks(n)), dim3(BLK), 0, s, n, bkey.p,
+                         cs_beg.p, bidx.p, bidx2.p, (const double4 *)nullptr,
+                         (const int *)nullptr, (double4 *)nullptr, (int *)nullptr,
+                         (int *)nullptr, 0);
+      cs_flags |= SPH_STAT_CSORT_ROWS;
+    } else {
+      hipLaunchKernelGGL(k_bin_keys, dim3(blocks(n)), dim3(BLK), 0, s, n, 0, kbn, xf.p, bkey.p,
+                         bidx.p, morton, cfg.dim);
+      size_t tb = 0;
+      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
+      tmp_reserve(tb);
+      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
+    }
     // twins of equal capacity: the swaps below then never reallocate (a growing twin would
     // cost a hipMalloc + a synchronising hipFree at every rebuild)
     if (mp) {  // the extra fields in the new order, packed before the permutation
@@ -1337,6 +1411,29 @@ struct sph_engine {
     // (mp: k_bin_copy packs the type into xb.w above bit 28, the list entries' MP_NMASK)
     SPH_REQUIRE(!mp || (long long)nall < MP_MAXALL, SPH_HIP_EOVERFLOW,
                 "multiphase lists index at most 2^28 atoms per rank (%d)", nall);
+    xpos.reserve(nall);
+    // the counting sort over the nqbins keys: its scan is qbeg itself, and its last pass
+    // writes the bin-ordered copy (k_cs_place<true>: k_bin_copy fused; SPH_TUNE_CSORT 2 keeps
+    // the two apart); else the radix sort, k_lower_bound and k_bin_copy
+    cs_flags &= ~SPH_STAT_CSORT_BINS;
+    if (cs_count(0, nall, nqbins, b, 0, 3, qbeg)) {
+      hipLaunchKernelGGL(k_cs_scatter, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
+                         (const int *)bkey2.p, qbeg.p, bidx.p);
+      if (csort == 2) {
+        hipLaunchKernelGGL(k_cs_place<false>, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
+                           qbeg.p, bidx.p, bidx2.p, (const double4 *)nullptr,
+                           (const int *)nullptr, (double4 *)nullptr, (int *)nullptr,
+                           (int *)nullptr, 0);
+        hipLaunchKernelGGL(k_bin_copy, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bidx2.p, xf.p,
+                           ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
+      } else {
+        hipLaunchKernelGGL(k_cs_place<true>, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
+                           qbeg.p, bidx.p, (int *)nullptr, xf.p, ty.p, xb.p, tb.p, xpos.p,
+                           mp ? 1 : 0);
+      }
+      cs_flags |= SPH_STAT_CSORT_BINS;
+      return;
+    }
     hipLaunchKernelGGL(k_bin_keys, dim3(blocks(nall)), dim3(BLK), 0, s, nall, 0, b, xf.p,
                        bkey.p, bidx.p, 0);
     int endbit = 1;
@@ -2649,6 +2746,8 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
     }
     SPH_HIP_TRY(hipHostMalloc(&e->h_scalar, sizeof(int)));
     SPH_HIP_TRY(hipHostMalloc(&e->h_small, 16 * sizeof(int)));
+    SPH_HIP_TRY(hipHostMalloc(&e->h_cs, 2 * sizeof(int)));
+    for (auto &ev : e->cs_ev) SPH_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   } catch (...) {
     delete e;
     throw;
@@ -2687,6 +2786,10 @@ int sph_engine_destroy(sph_engine *e) {
                   &e->ulist, &e->ucnt, &e->kcnt, &e->uilist, &e->uicnt})
     b->release();
   for (auto *b : {&e->bkey, &e->bkey2}) b->release();
+  for (auto *b : {&e->cs_cnt, &e->cs_beg, &e->cs_mx}) b->release();
+  for (auto ev : e->cs_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  if (e->h_cs) (void)hipHostFree(e->h_cs);
   for (auto *b : {&e->flags, &e->tmp, &e->cbs, &e->cbr, &e->flag2, &e->fl_in, &e->fl_bd}) b->release();
   e->snbr.release();
   e->snbi.release();
@@ -3231,6 +3334,9 @@ int sph_engine_stats_get(sph_engine *e, sph_engine_stats *st) {
   st->flags = (e->rho_fused_step >= 0 && e->rho_fused_step == e->step) ? SPH_STAT_RHO_FUSED : 0;
   if (e->blk) st->flags |= e->blk_flags;
   if (e->mp) st->flags |= e->mp_flags;
+  // (like the other families, not on the single-phase row path, whose flags stay bit 0 alone:
+  // sph_engine_csort_paths answers there too)
+  if (e->blk || e->mp) st->flags |= e->cs_flags;
   st->inner_refresh = e->inner_refreshes;
   SPH_API_END
 }
@@ -3340,8 +3446,19 @@ int sph_engine_tune(sph_engine *e, int key, int value) {
       SPH_REQUIRE(value >= 0, SPH_HIP_EINVAL, "sph_engine_tune: BLKUMF %d < 0", value);
       e->blkumf = value;
       break;
+    case SPH_TUNE_CSORT:
+      SPH_REQUIRE(value >= 0 && value <= 2, SPH_HIP_EINVAL, "sph_engine_tune: CSORT %d", value);
+      e->csort = value;
+      break;
     default: SPH_REQUIRE(false, SPH_HIP_EINVAL, "sph_engine_tune: unknown key %d", key);
   }
+  SPH_API_END
+}
+
+int sph_engine_csort_paths(sph_engine *e, int *mask) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && mask, SPH_HIP_EINVAL, "sph_engine_csort_paths: NULL argument");
+  *mask = e->cs_flags;
   SPH_API_END
 }
 

@@ -618,6 +618,77 @@ static __global__ void k_bin_copy(int n, const int *__restrict__ perm,
   if (xpos) xpos[j] = p;
 }
 
+// ---- counting sort of (key, 0..n-1) ------------------------------------------------------
+// The keys of bin_q and sort_owned are small dense integers (K of them, a few atoms each), so
+// the stable order DeviceRadixSort::SortPairs gives is had in four short passes: histogram
+// (k_cs_hist), one exclusive scan over K + 1 counts, scatter (k_cs_scatter), and a fix-up
+// (k_cs_place) that ranks every element among the indices of its own segment -- ascending
+// index within a key, element for element what the stable radix sort leaves.  The fix-up
+// reads a whole segment per element, so the host takes this path only while the longest
+// segment stays within CS_CAP (sph_engine::cs_count).
+#define CS_CAP 64  // longest segment the counting path orders (the host's limit)
+
+// key as k_bin_keys; slot = the element's arrival number within its key (any order); *mx =
+// the largest count above CS_CAP / 2 (0: none -- the common case raises no atomic on it)
+static __global__ void k_cs_hist(int n, Bins bn, const double4 *__restrict__ xf,
+                                 unsigned *__restrict__ key, int *__restrict__ slot,
+                                 int *__restrict__ cnt, int K, int *__restrict__ mx, int morton,
+                                 int hdim) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const double4 x = xf[k];
+  const int cx = bin_coord(x.x, bn.lo[0], bn.inv[0], bn.nb[0]);
+  const int cy = bin_coord(x.y, bn.lo[1], bn.inv[1], bn.nb[1]);
+  const int cz = bin_coord(x.z, bn.lo[2], bn.inv[2], bn.nb[2]);
+  unsigned q;
+  if (morton > 1)
+    q = hilbert_key(hdim, (unsigned)cx, (unsigned)cy, (unsigned)cz, morton - 1);
+  else
+    q = morton ? (spread3(cx) | (spread3(cy) << 1) | (spread3(cz) << 2))
+               : (unsigned)((cz * bn.nb[1] + cy) * bn.nb[0] + cx);
+  if (q >= (unsigned)K) q = (unsigned)K - 1;  // (never: the host sizes K to the key's range)
+  key[k] = q;
+  const int c = atomicAdd(&cnt[q], 1);
+  slot[k] = c;
+  if (c + 1 > CS_CAP / 2) atomicMax(mx, c + 1);
+}
+
+static __global__ void k_cs_scatter(int n, const unsigned *__restrict__ key,
+                                    const int *__restrict__ slot, const int *__restrict__ beg,
+                                    int *__restrict__ list) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  list[beg[key[k]] + slot[k]] = k;
+}
+
+// element k's place p = its segment's start + the number of smaller indices in the segment.
+// COPY = false: perm[p] = k (the sorted permutation).  COPY = true: k_bin_copy fused -- the
+// element's record goes straight to xb[p], tb[p], xpos[k] = p (positions and types read
+// coalesced; the permutation itself is not stored).
+template <bool COPY>
+__global__ void __launch_bounds__(256)
+k_cs_place(int n, const unsigned *__restrict__ key, const int *__restrict__ beg,
+           const int *__restrict__ list, int *__restrict__ perm,
+           const double4 *__restrict__ xf, const int *__restrict__ ty,
+           double4 *__restrict__ xb, int *__restrict__ tb, int *__restrict__ xpos, int tpack) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const unsigned q = key[k];
+  const int st = beg[q], en = beg[q + 1];
+  int r = 0;
+  for (int p = st; p < en; p++) r += list[p] < k ? 1 : 0;
+  const int p = st + r;
+  if (COPY) {
+    const double4 x = xf[k];
+    const int t = ty[k];
+    xb[p] = make_double4(x.x, x.y, x.z, (double)(tpack ? k | ((t - 1) << 28) : k));
+    tb[p] = t;
+    xpos[k] = p;
+  } else {
+    perm[p] = k;
+  }
+}
+
 // distance from coordinate v to bin b's slab along one axis (0 inside), shrunk by a margin
 __device__ __forceinline__ double slab_gap(double v, int b, int c, double lo, double size) {
   if (b == c) return 0.0;
