@@ -289,7 +289,9 @@ typedef struct {
   double heat_alpha[(SPH_MAXTYPES + 1) * (SPH_MAXTYPES + 1)];
   double heat_cut[(SPH_MAXTYPES + 1) * (SPH_MAXTYPES + 1)];
   /* body force per unit mass (fix gravity style), added in post_force: f += m*g, for the
-     types in gravity_mask (bit t set: type t is in the fix's group; 0 = every type) */
+     types in gravity_mask (bit t set: type t is in the fix's group; 0 = every type).
+     Single-phase engines only (the multiphase stack takes no body force from here: use
+     sph_engine_forcefix); it acts as a fix defined before every sph_engine_forcefix fix */
   double gravity[3];
   int gravity_mask;
   /* brick decomposition (procgrid[0]*procgrid[1]*procgrid[2] bricks, uniform split; 1 1 1 or
@@ -490,6 +492,9 @@ int sph_engine_setmeso(sph_engine *e, const sph_setmeso *fix);
 #define SPH_Q_DE 4
 #define SPH_Q_MASS 5    /* rmass, or mass[type] */
 #define SPH_Q_KE 6      /* 0.5 m |v|^2 */
+#define SPH_Q_VX 7      /* v (not vest): compute reduce ave vx, fix ave/spatial ... vx */
+#define SPH_Q_VY 8
+#define SPH_Q_VZ 9
 typedef struct {
   int quantity;        /* SPH_Q_* */
   int type_mask;
@@ -501,6 +506,81 @@ typedef struct {
   int64_t count;
 } sph_reduce_out;
 int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_reduce_out *out);
+
+/* fix setforce / fix addforce, constant style (FixSetForce::post_force,
+   fix_setforce.cpp:241-251; FixAddForce::post_force, fix_addforce.cpp:238, 269-282) on the
+   owned atoms of the group (type_mask) that the region selects at their current position.
+   Up to SPH_MAX_FORCEFIX fixes, all applied to each atom in call order by one kernel where
+   LAMMPS runs post_force: at the end of setup and in every step after the whole pair compute
+   (the engine's gathers leave nothing for a reverse comm to add), before that step's final
+   integrate -- the slot of sph_engine_setmeso, whose clamps touch other fields.  Only f's x,
+   y, z are written (a single-phase engine's drho is not); an atom no fix selects is not
+   stored; with no fix armed nothing is launched.  Created and migrated atoms meet the fixes
+   from the step they are owned.
+   cfg.gravity (single-phase engines only: the multiphase gathers take no body force) is added
+   inside the force pass, so it acts as a fix defined before every force fix: a later
+   setforce overwrites it, and a tally sees it.
+   per_mass: the added force is m_i * value[d], the product rounded on its own before the
+   add -- `variable bodyfx atom mass*${gx}` followed by f += sforce (poiseuille.lmp:57-58).
+   The sign change across a plane is two per_mass fixes on the two half-box blocks; regions
+   are closed, so an atom exactly on the shared plane gets both, where the reference's one
+   expression gives it 0.
+   nevery: the fix is applied in the steps with ntimestep % nevery == 0 (setup is step 0).
+   tally: the fix keeps foriginal[1..3] of setforce / foriginal[1..3] of addforce -- the
+   selected atoms' force just before this fix changed it, summed over this rank by a
+   fixed-shape two-stage reduction without atomics (identical runs give identical bits);
+   sph_engine_forcefix_total returns the sums of the last post_force that applied the fix
+   (combining ranks is the caller's).  Without tally nothing is reduced.  addforce's energy
+   foriginal[0] is not kept.
+   *id (may be NULL) receives the fix's index, 0, 1, ... in call order.  Before
+   sph_engine_setup.  SPH_HIP_EINVAL: after setup, more than SPH_MAX_FORCEFIX fixes, unknown
+   kind or region style, negative radius, per_mass or nevery != 1 on SET, ADD with comp_mask
+   != 7, nevery < 1; forcefix_total of a fix armed without tally, of an unknown id, or
+   before setup. */
+#define SPH_MAX_FORCEFIX 8
+#define SPH_FF_SET 0   /* fix setforce, constant style */
+#define SPH_FF_ADD 1   /* fix addforce, constant style */
+typedef struct {
+  int kind;            /* SPH_FF_* */
+  int comp_mask;       /* bit d set: component d has a value.  SET with a clear bit = NULL
+                          (left alone); ADD requires 7 */
+  double value[3];
+  int per_mass;        /* ADD only: value is per unit mass; added force = m_i * value[d]
+                          (m_i = rmass on multiphase engines, mass[type] otherwise) */
+  int nevery;          /* ADD only: applied when ntimestep % nevery == 0; >= 1 (SET: 1) */
+  int type_mask;       /* the fix's group, as sph_setmeso */
+  int region_mode;     /* 0 none, 1 region, 2 noregion (= !match) */
+  sph_region region;
+  int tally;           /* 1: keep the fix's foriginal force sums of each post_force */
+} sph_forcefix;
+int sph_engine_forcefix(sph_engine *e, const sph_forcefix *fix, int *id);
+int sph_engine_forcefix_total(sph_engine *e, int id, double out[3]);
+
+/* Layer profiles (fix ave/spatial ... <axis> origin delta <values>, one dimension, box
+   units): per layer, the atom count and the plain sum of each of nq quantities over the
+   owned atoms of this rank that the group and region select, in the state
+   sph_engine_get_atoms would return.  The layer of an atom (fix_ave_spatial.cpp:1006-1013):
+   its coordinate c along `axis`, remapped once if the axis is periodic (c < boxlo: c +=
+   prd; c >= boxhi: c -= prd), ibin = (int)((c - lo) * (1.0 / delta)) clamped to [0,
+   nlayers - 1] -- atoms outside [lo, lo + nlayers * delta) count in the edge layers.
+   count[nlayers]; sum[nq * nlayers], quantity-major (sum[q * nlayers + layer]).  Averaging
+   over samples and ranks is the caller's (`norm all` sums and divides).  The selected atoms'
+   indices are sorted by layer (stable) and each layer is folded in a fixed shape in index
+   order, no atomics: two calls on the same state return identical bits.  After setup.
+   SPH_HIP_EINVAL: axis outside 0..2, delta <= 0, nlayers < 1, nq outside [0,
+   SPH_MAX_PROFILE_Q] (0: counts only), an unknown quantity or region, before setup. */
+#define SPH_MAX_PROFILE_Q 8
+typedef struct {
+  int axis;            /* 0, 1, 2 */
+  double lo, delta;    /* fix ave/spatial's offset[0] and delta[0] */
+  int nlayers;
+  int type_mask;
+  int region_mode;
+  sph_region region;
+  int nq;
+  int quantity[SPH_MAX_PROFILE_Q];   /* SPH_Q_* */
+} sph_profile;
+int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, double *sum);
 
 /* Multiphase fields of the owned atoms in get_atoms order (any pointer may be NULL):
    rmass, cv, colorgradient (n*3), vest (n*3), type; *ninserted = atoms created so far. */

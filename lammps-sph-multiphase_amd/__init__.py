@@ -100,10 +100,14 @@ class EngineStats(C.Structure):
 SPH_REGION_SPHERE, SPH_REGION_BLOCK = 0, 1
 SPH_SET_RHO, SPH_SET_E, SPH_SET_T, SPH_SET_DE = 0, 1, 2, 3
 SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7)
+SPH_Q_VX, SPH_Q_VY, SPH_Q_VZ = 7, 8, 9
 SPH_MAX_SETMESO, SPH_MAX_REDUCE = 8, 16
+SPH_MAX_FORCEFIX, SPH_MAX_PROFILE_Q = 8, 8
+SPH_FF_SET, SPH_FF_ADD = 0, 1
 SET_FIELDS = {"rho": SPH_SET_RHO, "e": SPH_SET_E, "t": SPH_SET_T, "de": SPH_SET_DE}
 QUANTITIES = {"one": SPH_Q_ONE, "rho": SPH_Q_RHO, "e": SPH_Q_E, "t": SPH_Q_T, "de": SPH_Q_DE,
-              "mass": SPH_Q_MASS, "ke": SPH_Q_KE}
+              "mass": SPH_Q_MASS, "ke": SPH_Q_KE, "vx": SPH_Q_VX, "vy": SPH_Q_VY,
+              "vz": SPH_Q_VZ}
 
 
 class Region(C.Structure):
@@ -131,6 +135,46 @@ class ReduceOut(C.Structure):
     """sph_reduce_out"""
     _fields_ = [("sum", C.c_double), ("min", C.c_double), ("max", C.c_double),
                 ("count", C.c_int64)]
+
+
+class ForceFix(C.Structure):
+    """sph_forcefix: one fix setforce / addforce of constant style."""
+    _fields_ = [("kind", C.c_int), ("comp_mask", C.c_int), ("value", C.c_double * 3),
+                ("per_mass", C.c_int), ("nevery", C.c_int), ("type_mask", C.c_int),
+                ("region_mode", C.c_int), ("region", Region), ("tally", C.c_int)]
+
+
+class Profile(C.Structure):
+    """sph_profile: layers along one axis, quantities, group and region."""
+    _fields_ = [("axis", C.c_int), ("lo", C.c_double), ("delta", C.c_double),
+                ("nlayers", C.c_int), ("type_mask", C.c_int), ("region_mode", C.c_int),
+                ("region", Region), ("nq", C.c_int),
+                ("quantity", C.c_int * SPH_MAX_PROFILE_Q)]
+
+
+def layers(origin, delta, boxlo, boxhi):
+    """fix ave/spatial's layers along one axis in box units (fix_ave_spatial.cpp:880-898):
+    origin = "lower" | "center" | "upper" or a coordinate; -> (lo, nlayers), Engine.profile's
+    arguments.  The layers start at origin + k * delta and cover [boxlo, boxhi]."""
+    boxlo, boxhi, delta = float(boxlo), float(boxhi), float(delta)
+    if delta <= 0.0:
+        raise ValueError("delta must be positive")
+    named = {"lower": boxlo, "upper": boxhi, "center": 0.5 * (boxlo + boxhi)}
+    origin = named[origin] if isinstance(origin, str) else float(origin)
+    inv = 1.0 / delta
+    if origin < boxlo:
+        lo = origin + int((boxlo - origin) * inv) * delta
+    else:
+        lo = origin - int((origin - boxlo) * inv) * delta
+        if lo > boxlo:
+            lo -= delta
+    if origin < boxhi:
+        hi = origin + int((boxhi - origin) * inv) * delta
+        if hi < boxhi:
+            hi += delta
+    else:
+        hi = origin - int((origin - boxhi) * inv) * delta
+    return lo, int((hi - lo) * inv + 0.5)
 
 
 def _side(side):
@@ -181,6 +225,9 @@ EXPORTS = {
     # name: (restype, argtypes)
     "sph_engine_setmeso": (_i, [_vp, C.POINTER(SetMeso)]),
     "sph_engine_reduce": (_i, [_vp, _i, _vp, _vp]),
+    "sph_engine_forcefix": (_i, [_vp, C.POINTER(ForceFix), C.POINTER(_i)]),
+    "sph_engine_forcefix_total": (_i, [_vp, _i, _dp]),
+    "sph_engine_profile": (_i, [_vp, C.POINTER(Profile), _lp, _vp]),
     "sph_hip_last_error": (C.c_char_p, []),
     "sph_hip_abi_version": (_i, []),
     "sph_hip_device_count": (_i, []),
@@ -694,6 +741,62 @@ class Engine:
         _chk(self.L.sph_engine_reduce(self.h, n, C.cast(sel, C.c_void_p),
                                       C.cast(out, C.c_void_p)))
         return [dict(sum=o.sum, min=o.min, max=o.max, count=int(o.count)) for o in out[:n]]
+
+    def _forcefix(self, kind, values, per_mass, every, types, region, noregion, tally):
+        f = ForceFix()
+        f.kind = kind
+        for d, v in enumerate(values):
+            if v is not None:
+                f.comp_mask |= 1 << d
+                f.value[d] = float(v)
+        f.per_mass, f.nevery, f.tally = int(bool(per_mass)), int(every), int(bool(tally))
+        f.type_mask = _type_mask(types)
+        f.region_mode, f.region = _region_mode(region, noregion)
+        fid = _i(-1)
+        _chk(self.L.sph_engine_forcefix(self.h, C.byref(f), C.byref(fid)))
+        return fid.value
+
+    def setforce(self, fx, fy, fz, types=None, region=None, noregion=None, tally=False):
+        """fix setforce fx fy fz [region R] on the group of `types` (None = all); None for a
+        component is NULL (left alone).  tally: keep the selected atoms' force before the fix
+        (force_total).  Applied with the other force fixes in call order.  Before setup();
+        -> the fix's id."""
+        return self._forcefix(SPH_FF_SET, (fx, fy, fz), False, 1, types, region, noregion,
+                              tally)
+
+    def addforce(self, fx, fy, fz, per_mass=False, every=1, types=None, region=None,
+                 noregion=None, tally=False):
+        """fix addforce fx fy fz [every N] [region R]; per_mass: the values are per unit mass
+        (`variable bodyfx atom mass*${gx}`; fix addforce v_bodyfx ...).  Before setup(); -> the
+        fix's id."""
+        return self._forcefix(SPH_FF_ADD, (fx, fy, fz), per_mass, every, types, region,
+                              noregion, tally)
+
+    def force_total(self, fid):
+        """the tallying fix's foriginal force sums (3,) of the last post_force that applied it,
+        over this rank's owned atoms"""
+        out = np.zeros(3)
+        _chk(self.L.sph_engine_forcefix_total(self.h, int(fid), out))
+        return out
+
+    def profile(self, axis, lo, delta, nlayers, quantities, types=None, region=None,
+                noregion=None):
+        """fix ave/spatial's layers along `axis` (0, 1, 2 or "x", "y", "z"), lo and nlayers as
+        layers() gives them: -> (count (nlayers,) int64, sums (len(quantities), nlayers)) over
+        this rank's owned atoms of the group and region; quantities as reduce()'s."""
+        p = Profile()
+        p.axis = "xyz".index(axis) if isinstance(axis, str) else int(axis)
+        p.lo, p.delta, p.nlayers = float(lo), float(delta), int(nlayers)
+        p.type_mask = _type_mask(types)
+        p.region_mode, p.region = _region_mode(region, noregion)
+        p.nq = len(quantities)
+        for k, q in enumerate(quantities[:SPH_MAX_PROFILE_Q]):
+            p.quantity[k] = QUANTITIES[q] if isinstance(q, str) else int(q)
+        nl = max(p.nlayers, 1)
+        count = np.zeros(nl, dtype=np.int64)
+        sums = np.zeros((max(min(p.nq, SPH_MAX_PROFILE_Q), 1), nl))
+        _chk(self.L.sph_engine_profile(self.h, C.byref(p), count, sums.ctypes.data))
+        return count, sums[:p.nq]
 
     def get_atoms_multiphase(self):
         n = self.nlocal

@@ -190,6 +190,16 @@ struct sph_engine {
   // sph_engine_reduce: the blocks' partials and the folded results
   DBuf<ReducePart> red_part;
   DBuf<sph_reduce_out> red_out;
+  // fix setforce / addforce (sph_engine_forcefix), applied in call order by k_forcefix in
+  // the post_force slot; the tallying fixes' foriginal sums of their last post_force
+  ForceFixArgs ff{};
+  bool ff_tally = false;  // a fix keeps its foriginal sums
+  DBuf<double> ff_part, ff_tot;
+  // sph_engine_profile: layer keys and rows (sorted twins), the layers' counts and sums
+  DBuf<unsigned> pf_key, pf_key2;
+  DBuf<int> pf_idx, pf_idx2;
+  DBuf<long long> pf_cnt;
+  DBuf<double> pf_sum;
   bool pc_tags_agreed = false;  // bricks: tag_next agreed over the ranks (first call)
   std::vector<double> cv_by_tag;  // single-phase engines: the constant cv, for restarts
 
@@ -2499,6 +2509,44 @@ struct sph_engine {
                        (!mp && (force_mode & M_TAIT)) ? (const Coefs *)dc : nullptr);
   }
 
+  // the types' masses as configured (sc.mass is the body-force mass: 0 outside gravity_mask)
+  StepMass type_mass() const {
+    StepMass m;
+    for (int t = 0; t <= MAXT; t++) m.mass[t] = cfg.mass[t];
+    return m;
+  }
+
+  // FixSetForce / FixAddForce post_force of the armed fixes that are due in this step
+  // (ntimestep % nevery == 0) on the owned rows, after the pair compute has left f whole:
+  // the tallying fixes' foriginal sums first (k_forcefix_tally reads f as the chain finds
+  // it), then one launch of k_forcefix; none without a due fix
+  void post_force_forcefix() {
+    if (ff.nfix == 0) return;
+    ForceFixArgs a = ff;
+    a.active = 0;
+    bool tally = false;
+    for (int k = 0; k < ff.nfix; k++)
+      if (step % ff.fix[k].nevery == 0) {
+        a.active |= 1 << k;
+        tally = tally || ff.fix[k].tally;
+      }
+    if (a.active == 0) return;
+    Scope t(this, T_INT);
+    const StepMass tm = type_mass();
+    const double *m = mp ? (const double *)rm.p : nullptr;
+    if (tally) {
+      const int nb = (int)std::min<long>(blocks(nlocal), RED_MAXBLOCKS);
+      ff_part.reserve((size_t)RED_MAXBLOCKS * FF_NT);
+      if (nb)
+        hipLaunchKernelGGL(k_forcefix_tally, dim3(nb), dim3(RED_THREADS), 0, s, nlocal, a, xf.p,
+                           ty.p, m, tm, fo.p, ff_part.p);
+      hipLaunchKernelGGL(k_forcefix_final, dim3(1), dim3(64), 0, s, nb, a, ff_part.p, ff_tot.p);
+    }
+    if (nlocal)
+      hipLaunchKernelGGL(k_forcefix, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, a, xf.p, ty.p,
+                         m, tm, fo.p);
+  }
+
   bool rhosum_due() const {
     return cfg.rhosum_nstep > 0 && (step % cfg.rhosum_nstep) == 0;
   }
@@ -2522,6 +2570,11 @@ struct sph_engine {
                        cfg.stationary_mask, ty.p, vel.p, vr.p);
     pair_compute(rhosum_due(), /*setup=*/true);
     post_force_setmeso();  // (FixSetMeso::setup calls post_force)
+    if (ff_tally) {
+      ff_tot.reserve(FF_NT);
+      SPH_HIP_TRY(hipMemsetAsync(ff_tot.p, 0, FF_NT * sizeof(double), s));
+    }
+    post_force_forcefix();  // (FixSetForce::setup / FixAddForce::setup too)
     last_build = 0;
     setup_done = true;
   }
@@ -2559,6 +2612,7 @@ struct sph_engine {
         pair_compute(rhosum_due());
       }
       post_force_setmeso();
+      post_force_forcefix();
       refresh_inner(!pc && (step + 1 - last_build) % every == 0);
       if (timing && pending.size() > 4096) harvest();
     }
@@ -2780,6 +2834,14 @@ int sph_engine_destroy(sph_engine *e) {
   e->pc_cnt.release();
   e->red_part.release();
   e->red_out.release();
+  e->ff_part.release();
+  e->ff_tot.release();
+  e->pf_key.release();
+  e->pf_key2.release();
+  e->pf_idx.release();
+  e->pf_idx2.release();
+  e->pf_cnt.release();
+  e->pf_sum.release();
   for (auto *b : {&e->ty, &e->ty2, &e->tag, &e->tag2, &e->gowner, &e->gimg, &e->sel, &e->nsel,
                   &e->bidx, &e->bidx2, &e->cnt, &e->off, &e->nbr, &e->mx,
                   &e->ccnt, &e->qbeg, &e->tb, &e->xpos, &e->sel2, &e->rows_in, &e->rows_bd,
@@ -2967,7 +3029,7 @@ int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_re
   a.nsel = nsel;
   bool needs_cv = false;
   for (int k = 0; k < nsel; k++) {
-    SPH_REQUIRE(sel[k].quantity >= SPH_Q_ONE && sel[k].quantity <= SPH_Q_KE, SPH_HIP_EINVAL,
+    SPH_REQUIRE(sel[k].quantity >= SPH_Q_ONE && sel[k].quantity <= SPH_Q_VZ, SPH_HIP_EINVAL,
                 "sph_engine_reduce: selection %d: unknown quantity %d", k, sel[k].quantity);
     check_region("sph_engine_reduce", sel[k].region_mode, sel[k].region);
     a.sel[k] = sel[k];
@@ -2995,6 +3057,110 @@ int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_re
   SPH_HIP_TRY(hipMemcpyAsync(out, e->red_out.p, nsel * sizeof(sph_reduce_out),
                              hipMemcpyDeviceToHost, e->s));
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
+  SPH_API_END
+}
+
+int sph_engine_forcefix(sph_engine *e, const sph_forcefix *fix, int *id) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && fix, SPH_HIP_EINVAL, "sph_engine_forcefix: NULL argument");
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_forcefix: arm the fix before sph_engine_setup");
+  SPH_REQUIRE(fix->kind == SPH_FF_SET || fix->kind == SPH_FF_ADD, SPH_HIP_EINVAL,
+              "sph_engine_forcefix: unknown kind %d", fix->kind);
+  check_region("sph_engine_forcefix", fix->region_mode, fix->region);
+  SPH_REQUIRE(fix->nevery >= 1, SPH_HIP_EINVAL, "sph_engine_forcefix: nevery %d < 1",
+              fix->nevery);
+  SPH_REQUIRE((fix->comp_mask & ~7) == 0, SPH_HIP_EINVAL, "sph_engine_forcefix: comp_mask %d",
+              fix->comp_mask);
+  if (fix->kind == SPH_FF_SET)
+    SPH_REQUIRE(!fix->per_mass && fix->nevery == 1, SPH_HIP_EINVAL,
+                "sph_engine_forcefix: fix setforce has neither a per-mass value nor nevery");
+  else
+    SPH_REQUIRE(fix->comp_mask == 7, SPH_HIP_EINVAL,
+                "sph_engine_forcefix: fix addforce needs all three components (comp_mask 7)");
+  SPH_REQUIRE(e->ff.nfix < SPH_MAX_FORCEFIX, SPH_HIP_EINVAL,
+              "sph_engine_forcefix: more than %d fixes", SPH_MAX_FORCEFIX);
+  if (id) *id = e->ff.nfix;
+  e->ff.fix[e->ff.nfix++] = *fix;
+  if (fix->tally) e->ff_tally = true;
+  SPH_API_END
+}
+
+int sph_engine_forcefix_total(sph_engine *e, int id, double out[3]) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && out, SPH_HIP_EINVAL, "sph_engine_forcefix_total: NULL argument");
+  SPH_REQUIRE(id >= 0 && id < e->ff.nfix, SPH_HIP_EINVAL,
+              "sph_engine_forcefix_total: no fix %d", id);
+  SPH_REQUIRE(e->ff.fix[id].tally, SPH_HIP_EINVAL,
+              "sph_engine_forcefix_total: fix %d was armed without tally", id);
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_forcefix_total: call sph_engine_setup first");
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  SPH_HIP_TRY(hipMemcpyAsync(out, e->ff_tot.p + 3 * id, 3 * sizeof(double),
+                             hipMemcpyDeviceToHost, e->s));
+  SPH_HIP_TRY(hipStreamSynchronize(e->s));
+  SPH_API_END
+}
+
+int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, double *sum) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && p && count, SPH_HIP_EINVAL, "sph_engine_profile: NULL argument");
+  SPH_REQUIRE(p->axis >= 0 && p->axis <= 2, SPH_HIP_EINVAL, "sph_engine_profile: axis %d",
+              p->axis);
+  SPH_REQUIRE(p->delta > 0.0, SPH_HIP_EINVAL, "sph_engine_profile: delta %g <= 0", p->delta);
+  SPH_REQUIRE(p->nlayers >= 1, SPH_HIP_EINVAL, "sph_engine_profile: nlayers %d < 1",
+              p->nlayers);
+  SPH_REQUIRE(p->nq >= 0 && p->nq <= SPH_MAX_PROFILE_Q && (p->nq == 0 || sum), SPH_HIP_EINVAL,
+              "sph_engine_profile: nq %d outside [0,%d]", p->nq, SPH_MAX_PROFILE_Q);
+  bool needs_cv = false;
+  for (int q = 0; q < p->nq; q++) {
+    SPH_REQUIRE(p->quantity[q] >= SPH_Q_ONE && p->quantity[q] <= SPH_Q_VZ, SPH_HIP_EINVAL,
+                "sph_engine_profile: unknown quantity %d", p->quantity[q]);
+    needs_cv = needs_cv || p->quantity[q] == SPH_Q_T;
+  }
+  check_region("sph_engine_profile", p->region_mode, p->region);
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "sph_engine_profile: call sph_engine_setup first");
+  const double cvc = (!e->mp && needs_cv) ? e->uniform_cv("SPH_Q_T") : 1.0;
+  const int n = e->nlocal, nl = p->nlayers;
+  for (int l = 0; l < nl; l++) count[l] = 0;
+  for (size_t k = 0; k < (size_t)p->nq * nl; k++) sum[k] = 0.0;
+  if (n == 0) return SPH_HIP_OK;
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  ProfileArgs a{};
+  a.p = *p;
+  a.boxlo = e->box.lo[p->axis];
+  a.boxhi = e->box.hi[p->axis];
+  a.prd = e->box.prd[p->axis];
+  a.periodic = e->box.periodic[p->axis];
+  hipStream_t s = e->s;
+  e->pf_key.reserve(n);
+  e->pf_key2.reserve(n);
+  e->pf_idx.reserve(n);
+  e->pf_idx2.reserve(n);
+  e->pf_cnt.reserve(nl);
+  e->pf_sum.reserve((size_t)std::max(p->nq, 1) * nl);
+  hipLaunchKernelGGL(k_profile_keys, dim3(blocks(n)), dim3(BLK), 0, s, n, a, e->xf.p, e->ty.p,
+                     e->pf_key.p, e->pf_idx.p);
+  int eb = 1;  // (keys 0 .. nlayers; the radix sort is stable, so rows stay in order)
+  while (eb < 32 && (1u << eb) <= (unsigned)nl) eb++;
+  size_t tb = 0;
+  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, e->pf_key.p, e->pf_key2.p,
+                                                 e->pf_idx.p, e->pf_idx2.p, n, 0, eb, s));
+  e->tmp_reserve(tb);
+  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(e->tmp.p, tb, e->pf_key.p, e->pf_key2.p,
+                                                 e->pf_idx.p, e->pf_idx2.p, n, 0, eb, s));
+  hipLaunchKernelGGL(k_profile_fold, dim3(nl), dim3(RED_THREADS), 0, s, n, a, e->pf_key2.p,
+                     e->pf_idx2.p, e->vr.p, e->en.p, e->de.p, e->ty.p, e->vel.p,
+                     e->mp ? (const double *)e->rm.p : nullptr,
+                     e->mp ? (const double *)e->cvv.p : nullptr, cvc, e->type_mass(),
+                     e->pf_cnt.p, e->pf_sum.p);
+  SPH_HIP_TRY(hipGetLastError());
+  static_assert(sizeof(long long) == sizeof(int64_t), "count copy");
+  SPH_HIP_TRY(hipMemcpyAsync(count, e->pf_cnt.p, nl * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  if (p->nq)
+    SPH_HIP_TRY(hipMemcpyAsync(sum, e->pf_sum.p, (size_t)p->nq * nl * sizeof(double),
+                               hipMemcpyDeviceToHost, s));
+  SPH_HIP_TRY(hipStreamSynchronize(s));
   SPH_API_END
 }
 
