@@ -88,6 +88,13 @@ int sph_hip_taitwater_coeff(sph_hip_ctx *ctx, int visc_variant, const double *rh
 /* PairSPHHeatConduction::coeff/init_one: alpha and cut per pair ((nt+1)^2). */
 int sph_hip_heatconduction_coeff(sph_hip_ctx *ctx, const double *alpha, const double *cut,
                                  const double *mass);
+/* PairSPHIdealGas::coeff/init_one: viscosity and cut per pair ((nt+1)^2), mass = atom->mass.
+   init_one of this style mirrors cut but NOT viscosity (pair_sph_idealgas.cpp:214-225), so
+   the viscosity table is taken as LAMMPS holds it and read as viscosity[itype][jtype], i the
+   row atom of the staged list.  (With a table that differs from its transpose a HALF list
+   takes the atomics path, whose single evaluation per pair is the reference's.) */
+int sph_hip_idealgas_coeff(sph_hip_ctx *ctx, const double *viscosity, const double *cut,
+                           const double *mass);
 
 /* Stage per-atom inputs: nlocal owned then nghost ghost atoms (atom->x, atom->vest,
    atom->rho, atom->e, atom->type).  vest/rho/e may be NULL when the next compute does
@@ -153,6 +160,13 @@ int sph_hip_rhosum(sph_hip_ctx *ctx, double *rho);
 int sph_hip_taitwater(sph_hip_ctx *ctx, double *f, double *drho, double *de,
                       double *virial);
 int sph_hip_heatconduction(sph_hip_ctx *ctx, double *de);
+/* sph/idealgas (PairSPHIdealGas::compute, pair_sph_idealgas.cpp:48-175): the energy EOS
+   p = 0.4 e rho / m, sound speed c = sqrt(0.4 e / m), Lucy kernel, Monaghan viscosity on
+   approaching pairs.  f (nall*3), drho, de (nall) ACCUMULATED with the list semantics of
+   sph_hip_taitwater; reads the staged x, vest, rho, e, type -- SPH_HIP_EINVAL when the last
+   sph_hip_atoms was given no e.  virial may be NULL, else every pair is tallied TWICE, as
+   the reference's two ev_tally calls in a row do (:164-169). */
+int sph_hip_idealgas(sph_hip_ctx *ctx, double *f, double *drho, double *de, double *virial);
 
 /* ======================================================================================
  * 1b. Multiphase styles (atom_style meso/multiphase: per-atom rmass; quintic kernel).
@@ -556,6 +570,26 @@ typedef struct {
 int sph_engine_forcefix(sph_engine *e, const sph_forcefix *fix, int *id);
 int sph_engine_forcefix_total(sph_engine *e, int id, double out[3]);
 
+/* sph/idealgas as the engine's force style (shock_tube/shock2d.lmp: pair_style hybrid/overlay
+   sph/rhosum 1 sph/idealgas): it takes the slot of sph/taitwater in the step -- sph/rhosum
+   when due, forward comm of rho, the gas pass, post_force (setmeso, forcefix; cfg.gravity
+   inside the pass), final integrate -- on both kernel paths, with bricks, sort,
+   stationary_mask, rhosum_nstep 0 or N, sph_engine_pair_passes and restarts.  The per-atom
+   EOS term 0.4 e / m / rho is recomputed from the current e and rho before every gas pass.
+   viscosity and cut are read from the upper triangle (j >= i) and mirrored: the reference
+   leaves viscosity[j][i], j > i, unset, and the engine's both-sides gather needs a symmetric
+   table.  cut joins the neighbour cutoff (an engine without another style may be created
+   with no cut at all; sph_engine_setup then insists on this call).  Before sph_engine_setup.
+   SPH_HIP_EINVAL: after setup, a second call, cfg.tait_on, cfg.heat_on or cfg.mp set (one
+   force style per engine), a pair of types 1..ntypes with cut <= 0.
+   sph_engine_stats ms_tait / n_tait time the gas pass, and sph_engine_set_timing's bit 1
+   (taitwater) selects it. */
+typedef struct {
+  double viscosity[(SPH_MAXTYPES + 1) * (SPH_MAXTYPES + 1)];
+  double cut[(SPH_MAXTYPES + 1) * (SPH_MAXTYPES + 1)];
+} sph_engine_gas;
+int sph_engine_idealgas(sph_engine *e, const sph_engine_gas *gas);
+
 /* Layer profiles (fix ave/spatial ... <axis> origin delta <values>, one dimension, box
    units): per layer, the atom count and the plain sum of each of nq quantities over the
    owned atoms of this rank that the group and region select, in the state
@@ -618,7 +652,7 @@ int sph_engine_neighbor_counts(sph_engine *e, int *numneigh);
 int sph_engine_stats_get(sph_engine *e, sph_engine_stats *s);
 /* hipEvent timing of the kernel classes (adds an event pair per timed scope): on = 0 off,
    1 every class, (mask << 1) the classes in mask -- bit 0 rhosum, 1 taitwater (or the fused
-   multiphase gather), 2 heat, 3 integrate, 4 comm, 5 neighbor build / phase change */
+   multiphase gather, or the sph/idealgas pass of sph_engine_idealgas), 2 heat, 3 integrate, 4 comm, 5 neighbor build / phase change */
 int sph_engine_set_timing(sph_engine *e, int on);
 /* synchronise the engine's stream */
 int sph_engine_sync(sph_engine *e);

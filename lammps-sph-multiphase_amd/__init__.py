@@ -144,6 +144,12 @@ class ForceFix(C.Structure):
                 ("region_mode", C.c_int), ("region", Region), ("tally", C.c_int)]
 
 
+class EngineGas(C.Structure):
+    """sph_engine_gas: sph/idealgas viscosity and cut per type pair (upper triangle read)."""
+    _fields_ = [("viscosity", C.c_double * ((SPH_MAXTYPES + 1) ** 2)),
+                ("cut", C.c_double * ((SPH_MAXTYPES + 1) ** 2))]
+
+
 class Profile(C.Structure):
     """sph_profile: layers along one axis, quantities, group and region."""
     _fields_ = [("axis", C.c_int), ("lo", C.c_double), ("delta", C.c_double),
@@ -228,6 +234,9 @@ EXPORTS = {
     "sph_engine_forcefix": (_i, [_vp, C.POINTER(ForceFix), C.POINTER(_i)]),
     "sph_engine_forcefix_total": (_i, [_vp, _i, _dp]),
     "sph_engine_profile": (_i, [_vp, C.POINTER(Profile), _lp, _vp]),
+    "sph_engine_idealgas": (_i, [_vp, C.POINTER(EngineGas)]),
+    "sph_hip_idealgas_coeff": (_i, [_vp, _dp, _dp, _dp]),
+    "sph_hip_idealgas": (_i, [_vp, _dp, _dp, _dp, _vp]),
     "sph_hip_last_error": (C.c_char_p, []),
     "sph_hip_abi_version": (_i, []),
     "sph_hip_device_count": (_i, []),
@@ -397,6 +406,11 @@ class PairContext:
         _chk(self.L.sph_hip_heatconduction_coeff(self.h, self._t(alpha), self._t(cut),
                                                  self._t(mass)))
 
+    def idealgas_coeff(self, visc, cut, mass):
+        """sph/idealgas: visc and cut (ntypes+1, ntypes+1) as LAMMPS holds them -- visc is read
+        as visc[itype][jtype], i the row atom (init_one mirrors cut only)"""
+        _chk(self.L.sph_hip_idealgas_coeff(self.h, self._t(visc), self._t(cut), self._t(mass)))
+
     def atoms(self, nlocal, nghost, x, type_, vest=None, rho=None, e=None):
         x = np.ascontiguousarray(x, dtype=np.float64)
         t = np.ascontiguousarray(type_, dtype=np.int32)
@@ -476,6 +490,11 @@ class PairContext:
 
     def heatconduction(self, de):
         _chk(self.L.sph_hip_heatconduction(self.h, de))
+
+    def idealgas(self, f, drho, de, virial=None):
+        """sph/idealgas: f, drho, de accumulated as taitwater's; the virial tallied twice per
+        pair, as the reference does"""
+        _chk(self.L.sph_hip_idealgas(self.h, f, drho, de, _ptr(virial)))
 
     # -- multiphase styles (section 1b) --------------------------------------------------
     def atoms_multiphase(self, rmass, cv=None):
@@ -771,6 +790,15 @@ class Engine:
         fix's id."""
         return self._forcefix(SPH_FF_ADD, (fx, fy, fz), per_mass, every, types, region,
                               noregion, tally)
+
+    def idealgas(self, visc, cut):
+        """pair_style sph/idealgas as the engine's force style: visc and cut (ntypes+1,
+        ntypes+1), upper triangle read and mirrored.  Before setup(); not with tait, heat or
+        mp in the config."""
+        g = EngineGas()
+        _pair_table(g.viscosity, visc, self.cfg.ntypes)
+        _pair_table(g.cut, cut, self.cfg.ntypes)
+        _chk(self.L.sph_engine_idealgas(self.h, C.byref(g)))
 
     def force_total(self, fid):
         """the tallying fix's foriginal force sums (3,) of the last post_force that applied it,

@@ -1236,6 +1236,10 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
 // EXP (study builds, SPH_EXP): 1 = neighbour records synthesised from the slot (no LDS
 // reads), 2 = LDS reads with a trivial body, 3 = no staging loads (LDS image left as is).
 // Outputs meaningless.
+// GAS (sph/idealgas, pair_sph_idealgas.cpp:94-144; VISC = Monaghan): the same body with
+// xf.w = 0.4 e/m/rho (k_eos_gas) and the viscosity term's c_i + c_j.  The neighbour's
+// c_j = sqrt(e_j * 0.4/m_j) is computed once per STAGED record and kept in the fifth field of
+// the 80-byte image (+1024, where the heat mode keeps e_j); the sentinel's is 0.
 #define SPH_BLK_FORCE_PARAMS                                                              \
   int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, int ucap,                 \
       const unsigned short *__restrict__ snbr, int sstride, const int *__restrict__ rcnt,     \
@@ -1258,15 +1262,17 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
     ulist = uilist;  // (over their own union)
     ucnt = uicnt;
   }
-  constexpr bool TAIT = (MODE & M_TAIT) != 0;
+  constexpr bool GAS = (MODE & M_GAS) != 0;
+  constexpr bool TAIT = (MODE & (M_TAIT | M_GAS)) != 0;  // (the force / drho / de body)
   constexpr bool HEAT = (MODE & M_HEAT) != 0;
+  constexpr bool EIMG = HEAT || GAS;  // the image's fifth field: e_j (heat) | c_j (gas)
   constexpr int NTH = R * G;
-  constexpr int CQ = (HEAT ? BLK_CHE : BLK_CH) / 16;  // (= cq)
+  constexpr int CQ = (EIMG ? BLK_CHE : BLK_CH) / 16;  // (= cq)
   // one type, Monaghan viscosity, no heat term: the records carry rho_j / viscC (the row
   // rho_i / viscC), so fvisc = min(dvdr, 0) / ((rsq + eps)(rho_i + rho_j) / viscC) needs no
   // multiply by viscC per pair.  viscC = 0 never gets here: the host launches VISC =
   // BLK_VISC_NONE then (no viscosity term, as viscC * ... = 0 in the reference)
-  constexpr bool FOLDV = TAIT && !HEAT && NT1 && VISC == SPH_VISC_MONAGHAN;
+  constexpr bool FOLDV = TAIT && !HEAT && !GAS && NT1 && VISC == SPH_VISC_MONAGHAN;
   extern __shared__ __attribute__((aligned(16))) unsigned char blk_smem[];
   __shared__ TaitPair s_tp[(TAIT && !NT1) ? NT2 : 1];
   __shared__ HeatPair s_hp[(HEAT && !NT1) ? NT2 : 1];
@@ -1296,8 +1302,12 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   const double vsc = FOLDV ? 1.0 / cf->tait[3].viscC : 1.0;
   double4 vi = vr[rr];
   if (FOLDV) vi.w *= vsc;
-  const double ei = HEAT ? en[rr] : 0.0;
+  const double ei = EIMG ? en[rr] : 0.0;
   const int it = NT1 ? 1 : ty[rr];
+  // GAS: c = sqrt(e * 0.4/m) of the row atom, and of type t's atom with energy e
+  const double gk1 = (GAS && NT1) ? cf->gk[1] : 0.0;
+  auto gas_c = [&](double e, int t) { return sqrt1(e * (NT1 ? gk1 : cf->gk[t])); };
+  const double ci = GAS ? gas_c(ei, it) : 0.0;
   double4 qx[BLK_SP], qv[BLK_SP];
   double ge[BLK_SP];
   int gt[BLK_SP];
@@ -1306,12 +1316,12 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
     if (jj[k] >= 0) {
       qx[k] = xf[jj[k]];
       qv[k] = vr[jj[k]];
-      if (HEAT) ge[k] = en[jj[k]];
+      if (EIMG) ge[k] = en[jj[k]];
       if (!NT1) gt[k] = ty[jj[k]];
     }
   if (!NT1)
     for (int t = tid; t < nt1 * nt1; t += NTH) {
-      if (TAIT) s_tp[t] = cf->tait[t];
+      if (TAIT) s_tp[t] = GAS ? cf->gas[t] : cf->tait[t];
       if (HEAT) s_hp[t] = cf->heat[t];
     }
   unsigned char *const s_t = blk_smem + (size_t)((u0 + 16) >> 4) * cq * 16;
@@ -1320,7 +1330,8 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
     if (jj[k] >= 0) {
       const int sl = tid + k * NTH + 1;
       if (FOLDV) qv[k].w *= vsc;
-      blk_put<HEAT>(blk_smem, sl, cq, qx[k], qv[k], HEAT ? ge[k] : 0.0);
+      blk_put<EIMG>(blk_smem, sl, cq, qx[k], qv[k],
+                    GAS ? gas_c(ge[k], NT1 ? 1 : gt[k]) : (HEAT ? ge[k] : 0.0));
       if (!NT1) s_t[blk_q(sl, cq)] = (unsigned char)gt[k];
     }
   // window w's union records [w um, min(u, (w + 1) um)) from p0 on into slots 1, 2, ..
@@ -1330,20 +1341,21 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
       const int j = ul[p];
       double4 v = vr[j];
       if (FOLDV) v.w *= vsc;
-      blk_put<HEAT>(blk_smem, p - base + 1, cq, xf[j], v, HEAT ? en[j] : 0.0);
+      blk_put<EIMG>(blk_smem, p - base + 1, cq, xf[j], v,
+                    GAS ? gas_c(en[j], NT1 ? 1 : ty[j]) : (HEAT ? en[j] : 0.0));
       if (!NT1) s_t[blk_q(p - base + 1, cq)] = (unsigned char)ty[j];
     }
   };
   stage(0, tid + BLK_SP * NTH);
   if (tid == 0) {
-    blk_put_sentinel<HEAT>(blk_smem);
+    blk_put_sentinel<EIMG>(blk_smem);  // (e = 0 | c = 0)
     if (!NT1) s_t[0] = 1;
   }
   __syncthreads();
   TaitPair t1{};
   HeatPair h1{};
   if (NT1) {
-    if (TAIT) t1 = cf->tait[3];
+    if (TAIT) t1 = GAS ? cf->gas[3] : cf->tait[3];
     if (HEAT) h1 = cf->heat[3];
   }
   // F: sum of (d x) sp (- vel sv); E: sum of sp dvdr (- sv vel^2); D: sum of dvdr w; EH:
@@ -1366,7 +1378,7 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
       r.a2 = *reinterpret_cast<const double2 *>(rec + 512);
       r.a3 = *reinterpret_cast<const double2 *>(rec + 768);
     }
-    r.e = HEAT ? *reinterpret_cast<const double *>(rec + 1024) : 0.0;
+    r.e = EIMG ? *reinterpret_cast<const double *>(rec + 1024) : 0.0;
     return r;
   };
   auto pair = [&](const BlkRec &rc) {
@@ -1393,8 +1405,11 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
       const double dvdr = dx * velx + dy * vely + dz * velz;
       if (VISC == SPH_VISC_MONAGHAN) {
         // fvisc = viscC dvdr / ((rsq + eps)(rho_i + rho_j)) for dvdr < 0, else 0
+        // (GAS: visc h (c_i + c_j) min(dvdr, 0) / ((rsq + 0.01 h^2)(rho_i + rho_j)), viscC =
+        // -visc h and rc.e = c_j)
+        const double vC = GAS ? cc.viscC * (ci + rc.e) : cc.viscC;
         const double fv = FOLDV ? fmin(dvdr, 0.0) * rcp1((rsq + cc.eps) * (vi.w + a3.y))
-                                : (cc.viscC * fmin(dvdr, 0.0)) * rcp1((rsq + cc.eps) * (vi.w + a3.y));
+                                : (vC * fmin(dvdr, 0.0)) * rcp1((rsq + cc.eps) * (vi.w + a3.y));
         const double sp = NT1 ? (xi.w + a1.y + fv) * w : cc.mm * ((xi.w + a1.y + fv) * w);
         tfx = dx * sp;
         tfy = dy * sp;
@@ -1489,7 +1504,8 @@ __global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
 // the LDS latency.  The compiler otherwise settles at 98 VGPRs, 4 waves; 5 waves (<= 96
 // VGPRs) with the read-ahead measured 0.2550 vs 0.272-0.273 ms per launch, 6 waves 0.2435 /
 // 0.2497 vs 0.2632 / 0.2627 ms against that (profiles/r05/README.md).  The heat and
-// multi-type variants keep the default (at 96 VGPRs they would spill).
+// multi-type variants keep the default (at 96 VGPRs they would spill), and so does the gas
+// mode (M_GAS: the heat-size image and one more operand per pair).
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
 __global__ void __launch_bounds__(R * G) __attribute__((amdgpu_waves_per_eu(6, 6)))
 k_blk_force_w6(SPH_BLK_FORCE_PARAMS) {
@@ -1848,6 +1864,7 @@ inline void blk_force_n(int visc, int mode, hipStream_t s, const BlkArgs &k, con
       if (mor) blk_force_t<R, G, U, NCH, 1, M_TAIT | M_HEAT, NT1>(s, k, a);
       else blk_force_t<R, G, U, NCH, 0, M_TAIT | M_HEAT, NT1>(s, k, a);
       break;
+    case M_GAS: blk_force_t<R, G, U, NCH, 0, M_GAS, NT1>(s, k, a); break;
     default: blk_force_t<R, G, U, NCH, 0, M_HEAT, NT1>(s, k, a); break;
   }
 }

@@ -70,6 +70,38 @@ inline void coef_tait(Coefs &c, int dim, int nt, int visc_variant, const double 
     }
 }
 
+// pair_sph_idealgas.cpp:94-144.  mirror_visc: read viscosity from the upper triangle (the
+// engine's both-sides gather); else as the table holds it, visc[i][j] with i the row atom's
+// type (init_one of this style mirrors cut only, :241-250)
+inline void coef_gas(Coefs &c, int dim, int nt, const double *visc, const double *cut,
+                     const double *mass, bool mirror_visc) {
+  for (int i = 0; i <= nt; i++) {
+    c.gmass[i] = mass[i];
+    c.gk[i] = mass[i] != 0.0 ? 0.4 / mass[i] : 0.0;
+  }
+  for (int i = 1; i <= nt; i++)
+    for (int j = 1; j <= nt; j++) {
+      const double h = upper(cut, nt, i, j);
+      const double ih = 1.0 / h, ihsq = ih * ih;
+      TaitPair &t = c.gas[i * (nt + 1) + j];
+      t.cutsq = h * h;
+      t.h = h;
+      t.wK = (dim == 3) ? -25.066903536973515383e0 * ihsq * ihsq * ihsq * ih
+                        : -19.098593171027440292e0 * ihsq * ihsq * ihsq;
+      t.mm = -mass[i] * mass[j];
+      t.mj = mass[j];
+      t.mi = mass[i];
+      const double v = mirror_visc ? upper(visc, nt, i, j) : visc[i * (nt + 1) + j];
+      t.viscC = -v * h;
+      t.eps = 0.01 * h * h;
+      if (h <= 0.0) {  // no coefficients: zero weight, finite factors (see coef_rhosum)
+        t.wK = 0.0;
+        t.viscC = 0.0;
+        t.eps = 1.0;
+      }
+    }
+}
+
 // pair_sph_heatconduction.cpp:103-124
 inline void coef_heat(Coefs &c, int dim, int nt, const double *alpha, const double *cut,
                       const double *mass) {

@@ -45,6 +45,9 @@ struct sph_hip_ctx {
   Coefs hc{};
   Coefs *dc = nullptr;
   bool have_rho = false, have_tait = false, have_heat = false;
+  // sph/idealgas: coefficients set; its viscosity table equals its transpose (else a HALF
+  // list takes the atomics path); the staged atoms came with e
+  bool have_gas = false, gas_visc_sym = true, have_e = false;
   int tait_visc = SPH_VISC_MONAGHAN;
   int nlocal = 0, nghost = 0;
   bool have_atoms = false;

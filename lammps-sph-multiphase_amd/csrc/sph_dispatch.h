@@ -100,6 +100,8 @@ inline void launch_force_gdn(hipStream_t s, int visc, int mode, const ForceArgs 
       else launch_force_t<G, DIM, 0, M_TAIT | M_HEAT | M_HALF, NT1>(s, a);
       break;
     case M_HEAT | M_HALF: launch_force_t<G, DIM, 0, M_HEAT | M_HALF, NT1>(s, a); break;
+    case M_GAS: launch_force_t<G, DIM, 0, M_GAS, NT1>(s, a); break;
+    case M_GAS | M_HALF: launch_force_t<G, DIM, 0, M_GAS | M_HALF, NT1>(s, a); break;
     default: SPH_REQUIRE(false, SPH_HIP_EINVAL, "unsupported force mode %d", mode);
   }
 }

@@ -144,7 +144,10 @@ struct sph_engine {
   double sublo[3], subhi[3];
   double cutneighmax = 0.0, cutghost = 0.0;
   StepConst sc{};
-  int force_mode = 0;  // M_TAIT | M_HEAT
+  int force_mode = 0;  // M_TAIT | M_HEAT, or M_GAS alone (sph_engine_idealgas)
+  // the styles' largest cut per type pair ((ntypes+1)^2, upper triangle), kept so that
+  // sph_engine_idealgas can add its own before setup (set_cutoffs)
+  std::vector<double> cutmax_tab;
 
   // multiphase stack (cfg.mp, sph_engine_mp.h): per-atom rmass, cv, colorgradient of owned
   // atoms and ghosts, and the ghosts' v (comm vel yes)
@@ -418,10 +421,16 @@ struct sph_engine {
   // the block force pass's viscosity variant: one type with Monaghan viscosity and viscC = 0
   // (nu = 0 or c0 = 0) has no viscosity term at all (BLK_VISC_NONE)
   int blk_visc() const {
+    if (force_mode & M_GAS) return SPH_VISC_MONAGHAN;
     if (nt1() && cfg.tait_visc == SPH_VISC_MONAGHAN && hc.tait[3].viscC == 0.0)
       return BLK_VISC_NONE;
     return cfg.tait_visc;
   }
+
+  // the viscosity variant of the row and CSR passes (sph/idealgas has Monaghan's form)
+  int row_visc() const { return (force_mode & M_GAS) ? SPH_VISC_MONAGHAN : cfg.tait_visc; }
+  // the timer class of the force pass: taitwater's for every style that writes f
+  TimerClass force_class() const { return (force_mode & (M_TAIT | M_GAS)) ? T_TAIT : T_HEAT; }
 
   // ------------------------------------------------------------------------------------
   // Counting sort of xf[0, n) by the key of k_bin_keys (sph_engine_kernels.h, k_cs_*), first
@@ -1359,6 +1368,34 @@ struct sph_engine {
     }
   }
 
+  // The neighbour and ghost cutoffs from cutmax_tab, the checks that depend on them, and the
+  // bins: at create, and again when sph_engine_idealgas adds its cut
+  void set_cutoffs() {
+    const int nt = cfg.ntypes;
+    std::vector<double> cutmax = cutmax_tab;
+    // mirror upper triangle into a symmetric max-cut table (init_one semantics)
+    for (int i = 1; i <= nt; i++)
+      for (int j = 1; j < i; j++) cutmax[i * (nt + 1) + j] = cutmax[j * (nt + 1) + i];
+    // inner rows of the block path (sph_blk_kernels.h k_blk_inner): a sixteenth of the skin
+    // -- rows of ~110 instead of ~120 entries at C2 (with 16-entry walk chunks 114.5 instead
+    // of 128 pair evaluations), valid while no atom has moved skin/32 since the build
+    inner_margin = SPH_INNER_FRAC * cfg.skin;
+    cutneighmax = coef_cutneigh(hc, nt, cutmax.data(), cfg.skin, inner_margin);
+    SPH_REQUIRE(cutneighmax > 0.0, SPH_HIP_EINVAL, "no pair style enabled / zero cutoff");
+    cutghost = cutneighmax;  // CommBrick::setup: cutghost = cutneighmax (:166)
+    for (int k = 0; k < 3; k++) {
+      if (box.periodic[k])
+        SPH_REQUIRE(cutghost < box.prd[k], SPH_HIP_EINVAL,
+                    "ghost cutoff %g >= box length %g in dim %d (multi-hop borders unsupported)",
+                    cutghost, box.prd[k], k);
+      if (pg[k] > 1)  // CommBrick maxneed = 1: a brick must be wider than the ghost cut
+        SPH_REQUIRE(cutghost < subhi[k] - sublo[k], SPH_HIP_EINVAL,
+                    "ghost cutoff %g >= brick width %g in dim %d (multi-hop swaps unsupported)",
+                    cutghost, subhi[k] - sublo[k], k);
+    }
+    setup_bins_geometry();
+  }
+
   void setup_bins_geometry() {
     for (int k = 0; k < 3; k++) {
       double lo = sublo[k], hi = subhi[k];
@@ -1699,7 +1736,8 @@ struct sph_engine {
     return 0;
   }
   // the union image's chunk size / 16 (sph_blk_kernels.h): with the heat term's e array
-  int blk_cq() const { return ((force_mode & M_HEAT) ? BLK_CHE : BLK_CH) / 16; }
+  // or the gas mode's c
+  int blk_cq() const { return ((force_mode & (M_HEAT | M_GAS)) ? BLK_CHE : BLK_CH) / 16; }
   // The force pass's LDS image in union records (a multiple of 16) for unions of at most
   // maxu records, meanu on average: the whole largest union if it fits three workgroups per
   // CU (6 waves per SIMD); else three workgroups' image when the mean union fits it with
@@ -1921,7 +1959,7 @@ struct sph_engine {
         join();
       }
       {
-        Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);  // (includes the rho halo)
+        Scope t(this, force_class());  // (includes the rho halo)
         fork();
         blk_force(nt1(), blk_visc(), force_mode, s2, ki, row_args());
         forward_rho_multi();
@@ -1944,11 +1982,11 @@ struct sph_engine {
       join();
     }
     {
-      Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);  // (includes the rho halo)
+      Scope t(this, force_class());  // (includes the rho halo)
       fork();
-      row2_force(nt1(), cfg.tait_visc, force_mode, s2, bi);
+      row2_force(nt1(), row_visc(), force_mode, s2, bi);
       forward_rho_multi();
-      row2_force(nt1(), cfg.tait_visc, force_mode, s, bb);
+      row2_force(nt1(), row_visc(), force_mode, s, bb);
       join();
     }
   }
@@ -2056,16 +2094,22 @@ struct sph_engine {
     } else if (force_mode & M_TAIT) {
       hipLaunchKernelGGL(k_eos, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vr.p, ty.p, dc);
     }
+    // sph/idealgas: 0.4 e/m/rho of owned atoms and ghosts from the current e and rho (the
+    // ghosts' came with the halos), before EVERY gas pass -- e moves every step, whether or
+    // not rhosum was due
+    if ((force_mode & M_GAS) && nall)
+      hipLaunchKernelGGL(k_eos_gas, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vr.p, en.p,
+                         ty.p, dc);
     if (force_mode && setup) {
       setup_forces_full();
     } else if (force_mode && blk) {
-      Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);
+      Scope t(this, force_class());
       blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args());
     } else if (force_mode && use_row2()) {
-      Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);
-      row2_force(nt1(), cfg.tait_visc, force_mode, s, row2_args());
+      Scope t(this, force_class());
+      row2_force(nt1(), row_visc(), force_mode, s, row2_args());
     } else if (force_mode) {
-      Scope t(this, (force_mode & M_TAIT) ? T_TAIT : T_HEAT);
+      Scope t(this, force_class());
       ForceArgs a{};
       a.inum = nlocal;
       a.nlocal = nlocal;
@@ -2085,7 +2129,7 @@ struct sph_engine {
       a.gy = cfg.gravity[1];
       a.gz = cfg.gravity[2];
       a.virial = nullptr;
-      launch_force(cfg.dim, nt1(), s, cfg.tait_visc, force_mode, a);
+      launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a);
     } else {
       SPH_HIP_TRY(hipMemsetAsync(fo.p, 0, nlocal * sizeof(double4), s));
       SPH_HIP_TRY(hipMemsetAsync(de.p, 0, nlocal * sizeof(double), s));
@@ -2128,7 +2172,7 @@ struct sph_engine {
     a.gz = cfg.gravity[2];
     a.vso = vso.p;
     a.vsg = vsg.p;
-    launch_force(cfg.dim, nt1(), s, cfg.tait_visc, force_mode, a);
+    launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a);
   }
 
   // ---- multiphase stack -------------------------------------------------------------
@@ -2740,16 +2784,6 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
       e->cfg.mp = nullptr;
       coef_mp(e->hm, e->mpc, cfg->dim, nt, cutmax);
     }
-    // mirror upper triangle into a symmetric max-cut table (init_one semantics)
-    for (int i = 1; i <= nt; i++)
-      for (int j = 1; j < i; j++) cutmax[i * (nt + 1) + j] = cutmax[j * (nt + 1) + i];
-    // inner rows of the block path (sph_blk_kernels.h k_blk_inner): a sixteenth of the skin
-    // -- rows of ~110 instead of ~120 entries at C2 (with 16-entry walk chunks 114.5 instead
-    // of 128 pair evaluations), valid while no atom has moved skin/32 since the build
-    e->inner_margin = SPH_INNER_FRAC * cfg->skin;
-    e->cutneighmax = coef_cutneigh(c, nt, cutmax.data(), cfg->skin, e->inner_margin);
-    SPH_REQUIRE(e->cutneighmax > 0.0, SPH_HIP_EINVAL, "no pair style enabled / zero cutoff");
-    e->cutghost = e->cutneighmax;  // CommBrick::setup: cutghost = cutneighmax (:166)
     if (pgn > 1) {
       for (int k = 0; k < 3; k++) e->pg[k] = cfg->procgrid[k];
       e->nprocs = pgn;
@@ -2776,20 +2810,14 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
       };
       e->procneigh[k][0] = at(k == 0 ? -1 : 0, k == 1 ? -1 : 0, k == 2 ? -1 : 0);
       e->procneigh[k][1] = at(k == 0 ? 1 : 0, k == 1 ? 1 : 0, k == 2 ? 1 : 0);
-      if (e->box.periodic[k])
-        SPH_REQUIRE(e->cutghost < e->box.prd[k], SPH_HIP_EINVAL,
-                    "ghost cutoff %g >= box length %g in dim %d (multi-hop borders unsupported)",
-                    e->cutghost, e->box.prd[k], k);
-      if (e->pg[k] > 1)  // CommBrick maxneed = 1: a brick must be wider than the ghost cut
-        SPH_REQUIRE(e->cutghost < e->subhi[k] - e->sublo[k], SPH_HIP_EINVAL,
-                    "ghost cutoff %g >= brick width %g in dim %d (multi-hop swaps unsupported)",
-                    e->cutghost, e->subhi[k] - e->sublo[k], k);
     }
+    e->cutmax_tab = cutmax;
+    // (no style yet: sph_engine_idealgas brings the first cut; setup insists on one)
+    if (*std::max_element(cutmax.begin(), cutmax.end()) > 0.0) e->set_cutoffs();
     e->sc.dtv = cfg->dt;
     e->sc.dtf = 0.5 * cfg->dt * (cfg->ftm2v > 0 ? cfg->ftm2v : 1.0);  // fix_meso.cpp:63-66
     for (int t = 0; t <= nt; t++) e->sc.mass[t] = cfg->mass[t];
     e->sc.stationary_mask = cfg->stationary_mask;
-    e->setup_bins_geometry();
     SPH_HIP_TRY(hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking));
     SPH_HIP_TRY(hipMalloc(&e->dc, sizeof(Coefs)));
     SPH_HIP_TRY(hipMemcpy(e->dc, &e->hc, sizeof(Coefs), hipMemcpyHostToDevice));
@@ -3086,6 +3114,46 @@ int sph_engine_forcefix(sph_engine *e, const sph_forcefix *fix, int *id) {
   SPH_API_END
 }
 
+int sph_engine_idealgas(sph_engine *e, const sph_engine_gas *gas) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && gas, SPH_HIP_EINVAL, "sph_engine_idealgas: NULL argument");
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_idealgas: arm the style before sph_engine_setup");
+  SPH_REQUIRE(!(e->force_mode & M_GAS), SPH_HIP_EINVAL, "sph_engine_idealgas: already armed");
+  SPH_REQUIRE(!e->cfg.tait_on && !e->cfg.heat_on && !e->mp, SPH_HIP_EINVAL,
+              "sph_engine_idealgas: one force style per engine (tait_on, heat_on and mp off)");
+  const int nt = e->cfg.ntypes, n1 = nt + 1, M1 = SPH_MAXTYPES + 1;
+  std::vector<double> visc(n1 * n1, 0.0), cut(n1 * n1, 0.0);
+  for (int i = 1; i <= nt; i++)
+    for (int j = i; j <= nt; j++) {
+      SPH_REQUIRE(gas->cut[i * M1 + j] > 0.0, SPH_HIP_EINVAL,
+                  "sph_engine_idealgas: cut %g of types %d %d is not positive",
+                  gas->cut[i * M1 + j], i, j);
+      visc[i * n1 + j] = gas->viscosity[i * M1 + j];
+      cut[i * n1 + j] = gas->cut[i * M1 + j];
+    }
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  // (the cutoffs first: a cut the box cannot take leaves the engine as it was)
+  const std::vector<double> old = e->cutmax_tab;
+  for (size_t k = 0; k < cut.size(); k++) e->cutmax_tab[k] = std::max(old[k], cut[k]);
+  try {
+    e->set_cutoffs();
+  } catch (...) {
+    e->cutmax_tab = old;
+    if (*std::max_element(old.begin(), old.end()) > 0.0) e->set_cutoffs();
+    throw;
+  }
+  coef_gas(e->hc, e->cfg.dim, nt, visc.data(), cut.data(), e->cfg.mass, /*mirror_visc=*/true);
+  // (the rhosum epilogue still writes a Tait term, which k_eos_gas replaces: keep it finite)
+  for (int t = 0; t <= nt; t++) {
+    e->hc.rho0[t] = 1.0;
+    e->hc.B[t] = 0.0;
+  }
+  e->force_mode = M_GAS;
+  SPH_HIP_TRY(hipMemcpy(e->dc, &e->hc, sizeof(Coefs), hipMemcpyHostToDevice));
+  SPH_API_END
+}
+
 int sph_engine_forcefix_total(sph_engine *e, int id, double out[3]) {
   SPH_API_BEGIN
   SPH_REQUIRE(e && out, SPH_HIP_EINVAL, "sph_engine_forcefix_total: NULL argument");
@@ -3356,6 +3424,7 @@ int sph_engine_setup(sph_engine *e) {
   SPH_REQUIRE(!e->multi() || e->tr, SPH_HIP_ECOMM,
               "brick %d of %d: attach a communicator (sph_engine_comm_init / _comm_local) first",
               e->me, e->nprocs);
+  SPH_REQUIRE(e->cutneighmax > 0.0, SPH_HIP_EINVAL, "no pair style enabled / zero cutoff");
   SPH_HIP_TRY(hipSetDevice(e->device));
   e->setup();
   SPH_HIP_TRY(hipGetLastError());

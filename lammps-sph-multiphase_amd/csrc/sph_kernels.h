@@ -5,7 +5,8 @@
 //   xf[i] = {x, y, z, p/rho^2}   double4   (p/rho^2 = Tait pressure term, written by the
 //                                           rhosum epilogue or k_eos)
 //   vr[i] = {vx, vy, vz, rho}    double4   (v = atom->vest, the extrapolated velocity)
-//   ty[i] = type (int32), en[i] = e (double, heat conduction only)
+//   ty[i] = type (int32), en[i] = e (double; heat conduction, and sph/idealgas, whose
+//           xf[i].w is 0.4 e/m/rho instead: k_eos_gas)
 // Output of the force pass: fo[i] = {fx, fy, fz, drho} double4, de[i].
 //
 // Every kernel walks a CSR list with a G-lane group per row (G a power of two dividing the
@@ -59,6 +60,11 @@ struct Coefs {
   HeatPair heat[NT2];
   double cutneighsq[NT2];
   double cutinsq[NT2];     // (cut + inner margin)^2 of the block path's inner rows
+  // sph/idealgas (pair_sph_idealgas.cpp:94-144): the Lucy-kernel record of sph/taitwater with
+  // viscC = -visc*h (the pair's c_i + c_j multiplies it per pair); the types' mass and
+  // 0.4/mass (c = sqrt(e * 0.4/m))
+  TaitPair gas[NT2];
+  double gmass[MAXT + 1], gk[MAXT + 1];
 };
 
 // Blocks are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md, dispatch): give
@@ -230,15 +236,29 @@ static __global__ void k_eos(int n, double4 *__restrict__ xf, const double4 *__r
   xf[i].w = tait_p_over_rho2(vr[i].w, cf->rho0[t], cf->B[t]);
 }
 
+// sph/idealgas: the EOS term 0.4 e/m/rho (= p/rho^2 with p = 0.4 e rho/m) in the reference's
+// operation order (pair_sph_idealgas.cpp:94), of every atom before every gas pass -- e
+// changes every step
+static __global__ void k_eos_gas(int n, double4 *__restrict__ xf, const double4 *__restrict__ vr,
+                                 const double *__restrict__ en, const int *__restrict__ ty,
+                                 const Coefs *__restrict__ cf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  xf[i].w = 0.4 * en[i] / cf->gmass[ty[i]] / vr[i].w;
+}
+
 // ------------------------------------------------------------------------------------
-// Force pass: sph/taitwater (VISC=0 Monaghan, 1 Morris) and/or sph/heatconduction.
-// MODE bits: TAIT | HEAT | HALF.  FULL lists: overwrite (accum=0) or add (accum=1) the
+// Force pass: sph/taitwater (VISC=0 Monaghan, 1 Morris) and/or sph/heatconduction, or
+// sph/idealgas (GAS, VISC=0: the Monaghan body with xf.w = 0.4 e/m/rho from k_eos_gas and
+// the pair's c_i + c_j = sqrt(0.4 e_i/m_i) + sqrt(0.4 e_j/m_j) in the viscosity term; its
+// virial tallied twice, as the reference does).
+// MODE bits: TAIT | HEAT | HALF | GAS (GAS stands alone, or with HALF).  FULL lists: overwrite (accum=0) or add (accum=1) the
 // owned row's results.  HALF lists: atomics on both i and j (reference scatter), or, with
 // nojside, the i share only, added without atomics (the j share is then gathered by a
 // FULL-mode pass over the reverse half list: each pair value seen from j is exactly the
 // negated/mirrored j share -- the formulas are symmetric up to the sign of dx and dv).
 // ------------------------------------------------------------------------------------
-enum { M_TAIT = 1, M_HEAT = 2, M_HALF = 4 };
+enum { M_TAIT = 1, M_HEAT = 2, M_HALF = 4, M_GAS = 8 };
 
 // Neighbor::half_from_full_newton's test for a ghost j (neigh_derive.cpp:113-121): the pair
 // stays in i's half row iff j lies above i in z, then y, then x
@@ -260,20 +280,25 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
         double *__restrict__ de, int accum, const Coefs *__restrict__ cf, double gx,
         double gy, double gz, double *__restrict__ virial, int nojside,
         const double4 *__restrict__ vso, const double4 *__restrict__ vsg) {
-  constexpr bool TAIT = (MODE & M_TAIT) != 0;
+  constexpr bool GAS = (MODE & M_GAS) != 0;
+  constexpr bool TAIT = (MODE & (M_TAIT | M_GAS)) != 0;  // (the force / drho / de body)
   constexpr bool HEAT = (MODE & M_HEAT) != 0;
   constexpr bool HALF = (MODE & M_HALF) != 0;
   constexpr int U = UNROLL;
   __shared__ TaitPair s_t[(TAIT && !NT1) ? NT2 : 1];
   __shared__ HeatPair s_h[(HEAT && !NT1) ? NT2 : 1];
   __shared__ double s_mass[MAXT + 1];
+  __shared__ double s_gk[GAS ? MAXT + 1 : 1];
   const int nt1 = cf->ntypes + 1;
   if (!NT1)
     for (int t = threadIdx.x; t < nt1 * nt1; t += blockDim.x) {
-      if (TAIT) s_t[t] = cf->tait[t];
+      if (TAIT) s_t[t] = GAS ? cf->gas[t] : cf->tait[t];
       if (HEAT) s_h[t] = cf->heat[t];
     }
-  for (int t = threadIdx.x; t < nt1; t += blockDim.x) s_mass[t] = cf->mass[t];
+  for (int t = threadIdx.x; t < nt1; t += blockDim.x) {
+    s_mass[t] = cf->mass[t];
+    if (GAS) s_gk[t] = cf->gk[t];
+  }
   __syncthreads();
   const int row = (int)((xcd_block() * blockDim.x + threadIdx.x) / G);
   const int lane = threadIdx.x & (G - 1);
@@ -281,14 +306,15 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
   const int i = ilist ? ilist[row] : row;
   const double4 xi = xf[i];
   const double4 vi = vr[i];
-  const double ei = HEAT ? en[i] : 0.0;
+  const double ei = (HEAT || GAS) ? en[i] : 0.0;
   const int it = NT1 ? 1 : ty[i];
   TaitPair t1{};
   HeatPair h1{};
   if (NT1) {
-    if (TAIT) t1 = cf->tait[3];
+    if (TAIT) t1 = GAS ? cf->gas[3] : cf->tait[3];
     if (HEAT) h1 = cf->heat[3];
   }
+  const double ci = GAS ? fast_sqrt(ei * s_gk[it]) : 0.0;
   const int beg = off[row], end = off[row + 1];
   double fx = 0.0, fy = 0.0, fz = 0.0, drho = 0.0, dE = 0.0;
   double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0, v4 = 0.0, v5 = 0.0;
@@ -303,7 +329,7 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
     for (int u = 0; u < U; u++) {
       xj[u] = xf[jv[u]];
       vj[u] = vr[jv[u]];
-      ej[u] = HEAT ? en[jv[u]] : 0.0;
+      ej[u] = (HEAT || GAS) ? en[jv[u]] : 0.0;
       tj[u] = NT1 ? 1 : ty[jv[u]];
     }
 #pragma unroll
@@ -342,7 +368,9 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
         double fpair, deltaE, fvx = 0.0, fvy = 0.0, fvz = 0.0;
         if (VISC == SPH_VISC_MONAGHAN) {
           // mu = h dvdr/(rsq+0.01h^2); fvisc = -visc (c_i+c_j) mu/(rho_i+rho_j), dvdr < 0
-          const double q = (c.viscC * dvdr) * fast_rcp((rsq + c.eps) * (vi.w + vj[u].w));
+          // (GAS: viscC = -visc h, times c_i + c_j of the pair)
+          const double vc = GAS ? c.viscC * (ci + fast_sqrt(ej[u] * s_gk[tj[u]])) : c.viscC;
+          const double q = (vc * dvdr) * fast_rcp((rsq + c.eps) * (vi.w + vj[u].w));
           const double fvisc = dvdr < 0. ? q : 0.0;
           fpair = c.mm * (xi.w + xj[u].w + fvisc) * wfd;
           deltaE = -0.5 * fpair * dvdr;
@@ -371,7 +399,8 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
         }
         if (virial) {
           const double s = (!HALF || newton || j < nlocal) ? 1.0 : 0.5;
-          const double sf = HALF ? s * fpair : 0.5 * fpair;
+          // (GAS: two ev_tally calls per pair, pair_sph_idealgas.cpp:164-169)
+          const double sf = (GAS ? 2.0 : 1.0) * (HALF ? s * fpair : 0.5 * fpair);
           v0 += sf * dx * dx;
           v1 += sf * dy * dy;
           v2 += sf * dz * dz;

@@ -180,6 +180,23 @@ int sph_hip_heatconduction_coeff(sph_hip_ctx *c, const double *alpha, const doub
   SPH_API_END
 }
 
+int sph_hip_idealgas_coeff(sph_hip_ctx *c, const double *viscosity, const double *cut,
+                           const double *mass) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(c && viscosity && cut && mass, SPH_HIP_EINVAL,
+              "sph_hip_idealgas_coeff: NULL argument");
+  coef_gas(c->hc, c->dim, c->ntypes, viscosity, cut, mass, /*mirror_visc=*/false);
+  for (int t = 0; t <= c->ntypes; t++) c->hc.mass[t] = mass[t];
+  c->gas_visc_sym = true;
+  const int n1 = c->ntypes + 1;
+  for (int i = 1; i < n1; i++)
+    for (int j = 1; j < i; j++)
+      if (c->hc.gas[i * n1 + j].viscC != c->hc.gas[j * n1 + i].viscC) c->gas_visc_sym = false;
+  c->have_gas = true;
+  c->coef_dirty = true;
+  SPH_API_END
+}
+
 // LAMMPS' per-atom arrays (x, vest: nall*3; rho, e: nall; NULL = zeros) -> the gather
 // records, with the type range checked on the way (bad |= 1)
 static __global__ void k_pack_atoms(int nall, const double *__restrict__ x,
@@ -287,6 +304,7 @@ int sph_hip_atoms(sph_hip_ctx *c, int nlocal, int nghost, const double *x, const
   c->nghost = nghost;
   c->have_mp_atoms = false;  // rmass/cv must be restaged for the new atom set
   c->have_atoms = false;
+  c->have_e = e != nullptr;
   if (nall == 0) {
     c->have_atoms = true;
     return SPH_HIP_OK;
@@ -333,6 +351,7 @@ int sph_hip_atoms_update(sph_hip_ctx *c, const double *x, const double *vest,
   SPH_REQUIRE(c->have_atoms, SPH_HIP_EINVAL, "sph_hip_atoms_update: no atoms staged");
   SPH_HIP_TRY(hipSetDevice(c->device));
   const size_t nall = (size_t)c->nlocal + c->nghost;
+  if (e) c->have_e = true;
   if (nall == 0) return SPH_HIP_OK;  // (rmass / cv of the same atom set stay staged)
   c->raw.reserve(8 * nall);
   double *const rx = c->raw.p, *const rv = rx + 3 * nall, *const rr = rv + 3 * nall,
@@ -532,6 +551,10 @@ static void run_force(sph_hip_ctx *c, int mode, double *f, double *drho, double 
   if (mode & M_TAIT)  // p/rho^2 of every atom (owned + ghost) from the staged rho
     hipLaunchKernelGGL(k_eos, dim3((nall + 255) / 256), dim3(256), 0, c->stream, nall, c->xf.p,
                        c->vr.p, c->ty.p, c->dc);
+  if (mode & M_GAS)  // 0.4 e/m/rho of every atom from the staged e and rho
+    hipLaunchKernelGGL(k_eos_gas, dim3((nall + 255) / 256), dim3(256), 0, c->stream, nall,
+                       c->xf.p, c->vr.p, c->en.p, c->ty.p, c->dc);
+  const bool hasf = (mode & (M_TAIT | M_GAS)) != 0;  // (the style writes f and drho)
   ForceArgs a{};
   a.inum = c->inum;
   a.nlocal = c->nlocal;
@@ -548,7 +571,8 @@ static void run_force(sph_hip_ctx *c, int mode, double *f, double *drho, double 
   a.accum = 0;
   a.cf = c->dc;
   a.virial = virial ? c->virial.p : nullptr;
-  const bool rev = c->list_kind == SPH_LIST_HALF && sph_rev_on();
+  const bool rev = c->list_kind == SPH_LIST_HALF && sph_rev_on() &&
+                   (!(mode & M_GAS) || c->gas_visc_sym);
   if (rev) c->build_rev();  // timed with the kernels (once per list upload)
   if (c->list_kind == SPH_LIST_HALF) mode |= M_HALF;
   a.nojside = rev ? 1 : 0;
@@ -570,10 +594,10 @@ static void run_force(sph_hip_ctx *c, int mode, double *f, double *drho, double 
   double hv[6] = {0, 0, 0, 0, 0, 0};
   {  // results added straight into the caller's (mapped) arrays when every one is registered
     const size_t nb = (size_t)nall * sizeof(double);
-    double *mf = (mode & M_TAIT) ? static_cast<double *>(c->mapped(f, 3 * nb)) : nullptr;
-    double *md = (mode & M_TAIT) && drho ? static_cast<double *>(c->mapped(drho, nb)) : nullptr;
+    double *mf = hasf ? static_cast<double *>(c->mapped(f, 3 * nb)) : nullptr;
+    double *md = hasf && drho ? static_cast<double *>(c->mapped(drho, nb)) : nullptr;
     double *me = de ? static_cast<double *>(c->mapped(de, nb)) : nullptr;
-    const bool ok = (!(mode & M_TAIT) || (mf && (md || !drho))) && (me || !de);
+    const bool ok = (!hasf || (mf && (md || !drho))) && (me || !de);
     if (ok) {
       const bool half = c->list_kind == SPH_LIST_HALF;
       const int rows = half ? nall : c->inum;
@@ -588,7 +612,7 @@ static void run_force(sph_hip_ctx *c, int mode, double *f, double *drho, double 
       return;
     }
   }
-  if (mode & M_TAIT) {
+  if (hasf) {
     c->h4.resize(nall);
     SPH_HIP_TRY(hipMemcpyAsync(c->h4.data(), c->fo.p, nall * sizeof(double4), hipMemcpyDeviceToHost, c->stream));
   }
@@ -599,7 +623,7 @@ static void run_force(sph_hip_ctx *c, int mode, double *f, double *drho, double 
   c->tread();
   const int n = (c->list_kind == SPH_LIST_HALF) ? nall : 0;
   auto add_atom = [&](int i) {
-    if (mode & M_TAIT) {
+    if (hasf) {
       f[3 * i] += c->h4[i].x;
       f[3 * i + 1] += c->h4[i].y;
       f[3 * i + 2] += c->h4[i].z;
@@ -622,6 +646,17 @@ int sph_hip_taitwater(sph_hip_ctx *c, double *f, double *drho, double *de, doubl
   SPH_REQUIRE(c->have_tait, SPH_HIP_EINVAL, "sph_hip_taitwater: coefficients not set");
   SPH_REQUIRE(c->list_kind >= 0, SPH_HIP_EINVAL, "sph_hip_taitwater: no neighbor list staged");
   run_force(c, M_TAIT, f, drho, de, virial);
+  SPH_API_END
+}
+
+int sph_hip_idealgas(sph_hip_ctx *c, double *f, double *drho, double *de, double *virial) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(c && f && drho && de, SPH_HIP_EINVAL, "sph_hip_idealgas: bad argument");
+  SPH_REQUIRE(c->have_gas, SPH_HIP_EINVAL, "sph_hip_idealgas: coefficients not set");
+  SPH_REQUIRE(c->list_kind >= 0, SPH_HIP_EINVAL, "sph_hip_idealgas: no neighbor list staged");
+  SPH_REQUIRE(c->have_atoms && c->have_e, SPH_HIP_EINVAL,
+              "sph_hip_idealgas: the staged atoms carry no e (sph_hip_atoms was given NULL)");
+  run_force(c, M_GAS, f, drho, de, virial);
   SPH_API_END
 }
 

@@ -267,16 +267,22 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
              const double *__restrict__ en, const Coefs *__restrict__ cf,
              double4 *__restrict__ fo, double *__restrict__ de, double gx, double gy,
              double gz, const int *__restrict__ rows, int tbits) {
-  constexpr bool TAIT = (MODE & M_TAIT) != 0;
+  // GAS (sph/idealgas): the Monaghan body with xf.w = 0.4 e/m/rho (k_eos_gas) and the pair's
+  // c_i + c_j, c = sqrt(e * 0.4/m), in the viscosity term; e_j gathered as the heat term's
+  constexpr bool GAS = (MODE & M_GAS) != 0;
+  constexpr bool TAIT = (MODE & (M_TAIT | M_GAS)) != 0;  // (the force / drho / de body)
   constexpr bool HEAT = (MODE & M_HEAT) != 0;
   __shared__ TaitPair s_t[(TAIT && !NT1) ? NT2 : 1];
   __shared__ HeatPair s_h[(HEAT && !NT1) ? NT2 : 1];
+  __shared__ double s_gk[(GAS && !NT1) ? MAXT + 1 : 1];
   const int nt1 = cf->ntypes + 1;
   if (!NT1) {
     for (int t = threadIdx.x; t < nt1 * nt1; t += blockDim.x) {
-      if (TAIT) s_t[t] = cf->tait[t];
+      if (TAIT) s_t[t] = GAS ? cf->gas[t] : cf->tait[t];
       if (HEAT) s_h[t] = cf->heat[t];
     }
+    if (GAS)
+      for (int t = threadIdx.x; t < nt1; t += blockDim.x) s_gk[t] = cf->gk[t];
     __syncthreads();
   }
   const int idx = (int)((xcd_block() * blockDim.x + threadIdx.x) / G);
@@ -288,20 +294,22 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
   const Rsrc rx = make_rsrc(xf, nbytes<double4>(nall));
   const Rsrc rv = make_rsrc(vr, nbytes<double4>(nall));
   const Rsrc rt = make_rsrc(ty, nbytes<int>(nall));
-  const Rsrc re = make_rsrc(en, HEAT ? nbytes<double>(nall) : 0u);
+  const Rsrc re = make_rsrc(en, (HEAT || GAS) ? nbytes<double>(nall) : 0u);
   const int rr = rows ? rows[live ? idx : n - 1] : (live ? idx : n - 1);
   const int row = rr;
   const bool tb = !NT1 && tbits != 0;
   const double4 xi = xf[rr];
   const double4 vi = vr[rr];
-  const double ei = HEAT ? en[rr] : 0.0;
+  const double ei = (HEAT || GAS) ? en[rr] : 0.0;
   const int it = NT1 ? 1 : ty[rr];
   TaitPair t1{};
   HeatPair h1{};
   if (NT1) {
-    if (TAIT) t1 = cf->tait[3];
+    if (TAIT) t1 = GAS ? cf->gas[3] : cf->tait[3];
     if (HEAT) h1 = cf->heat[3];
   }
+  const double gk1 = (GAS && NT1) ? cf->gk[1] : 0.0;
+  const double ci = GAS ? sqrt1(ei * (NT1 ? gk1 : s_gk[it])) : 0.0;
   // stride > 0: fixed-stride rows (row rr at rr*stride, rcnt[rr] entries), else CSR
   const int beg = stride > 0 ? rr * stride : off[rr];
   const int end = live ? (stride > 0 ? beg + rcnt[rr] : off[rr + 1]) : beg;
@@ -330,7 +338,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
         xj[u] = ld_d4(rx, o * 32u);
         vj[u] = ld_d4(rv, o * 32u);
       }
-      ej[u] = HEAT ? ld_d1(re, o * 8u) : 0.0;
+      ej[u] = (HEAT || GAS) ? ld_d1(re, o * 8u) : 0.0;
       tj[u] = NT1 ? 1 : (tb ? ent_type((unsigned)jn[u], nt1 - 1) : ld_i32(rt, o * 4u));
     }
     chunk_idx<G, U, IV>(rn, k0 + G * U, lane, jn);
@@ -359,7 +367,10 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
         const double velx = vi.x - vj[u].x, vely = vi.y - vj[u].y, velz = vi.z - vj[u].z;
         const double dvdr = dx * velx + dy * vely + dz * velz;
         if (VISC == SPH_VISC_MONAGHAN) {
-          const double q = (c.viscC * dvdr) * rcp1((rsq + c.eps) * (vi.w + vj[u].w));
+          // (GAS: viscC = -visc h, times c_i + c_j; a masked slot's e_j is an atom's or 0)
+          const double vc = GAS ? c.viscC * (ci + sqrt1(ej[u] * (NT1 ? gk1 : s_gk[tj[u]])))
+                                : c.viscC;
+          const double q = (vc * dvdr) * rcp1((rsq + c.eps) * (vi.w + vj[u].w));
           const double fvisc = dvdr < 0. ? q : 0.0;
           const double fpair = c.mm * (xi.w + xj[u].w + fvisc) * wfd;
           fx += dx * fpair;
@@ -476,6 +487,7 @@ inline void row2_force_n(int visc, int mode, hipStream_t s, const Row2Args &b) {
       if (mor) row2_force_t<G, U, 1, M_TAIT | M_HEAT, NT1, LP, IV, 0>(s, b);
       else row2_force_t<G, U, 0, M_TAIT | M_HEAT, NT1, LP, IV, 0>(s, b);
       break;
+    case M_GAS: row2_force_t<G, U, 0, M_GAS, NT1, LP, IV, 0>(s, b); break;
     default: row2_force_t<G, U, 0, M_HEAT, NT1, LP, IV, 0>(s, b); break;
   }
 }
