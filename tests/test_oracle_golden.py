@@ -204,6 +204,80 @@ def test_oracle_vs_reference_fresh_seed(po, ref, case):
 
 
 @pytest.mark.ref
+@pytest.mark.parametrize("case", ["mixed3", "mixed3_morris", "mixed8"])
+def test_oracle_vs_reference_pair_tables(po, ref, case):
+    """Per-pair tables whose entries all differ (tables_util: unequal cuts per pair and per
+    style, absent pairs, 3 and 8 types, per-type mass / rho0 / c0 distinct): the lists against
+    ref_neigh_full with the per-pair cutneighsq, and rhosum, taitwater / morris and heat
+    conduction bit-exact.
+
+    The reference's styles run under hybrid/overlay, which hands each sub-style a SKIP list
+    holding only the rows and pairs it has coefficients for; the harness has no hybrid.  So
+    each style of the reference is fed that list (tables_util.style_list; rhosum through
+    ref_rhosum_skip with the rows of the types it has a pair for, its other coefficients
+    poisoned with NaN), in the way scenarios.skip_list_case does, while the restatement gets
+    the unfiltered list and the table with cut 0 for the absent pairs, as the engine's
+    oracle (RefRun) calls it."""
+    import tables_util as tu
+    s, ph = tu.case(case, 7)
+    tu.premises(s, ph)
+    P = prepared(s, ph)
+    g = P["g"]
+    nt = s.ntypes
+    off = np.zeros(g.nlocal + 1, dtype=np.int64)
+    args = (s.dim, nt, g.nlocal, g.nghost, np.ascontiguousarray(g.x), g.type, s.boxlo, s.boxhi,
+            s.boxlo, s.boxhi, P["cmax"], np.ascontiguousarray(P["cns"]))
+    tot = ref.ref_neigh_full(*args, off, None, 0)
+    nb = np.zeros(max(tot, 1), dtype=np.int32)
+    ref.ref_neigh_full(*args, off, nb.ctypes.data, tot)
+    assert np.array_equal(off, P["foff"])
+    assert np.array_equal(sorted_rows(off, nb[:tot]), sorted_rows(off, P["fnb"]))
+    # rhosum: rows of the types with a pair, pairs with a coefficient
+    rc = np.ascontiguousarray(ph.rhosum_cut)
+    keep = ph.rho_keep(nt)
+    assert keep[1:].any() == (case == "mixed8")
+    soff, snb = tu.style_list(g, P["foff"], P["fnb"], rc)
+    rows = np.nonzero(~keep[s.type])[0].astype(np.int32)
+    roff = np.zeros(len(rows) + 1, dtype=np.int64)
+    roff[1:] = np.cumsum(np.diff(soff)[rows])
+    assert roff[-1] == soff[-1]                  # (the skipped types' rows are empty)
+    rr = P["rho_all"].copy()
+    ref.ref_rhosum_skip(s.dim, nt, g.nlocal, g.nghost, np.ascontiguousarray(g.x), g.type,
+                        s.mass, rc.ravel(), len(rows), rows, roff, snb,
+                        np.ascontiguousarray(keep, dtype=np.int32),
+                        np.ascontiguousarray((rc <= 0).ravel(), dtype=np.int32), rr)
+    with np.errstate(all="ignore"):              # (skipped types' self terms: h = 0)
+        ro = po.rhosum(s.dim, g, nt, s.mass, rc, P["foff"], P["fnb"])
+    ro[keep[s.type]] = P["rho_all"][:s.n][keep[s.type]]
+    assert np.array_equal(rr[:g.nlocal], ro)
+    # taitwater / morris and heat conduction: half lists, Newton on
+    hoff, hnb = tu.style_list(g, P["hoff"], P["hnb"], ph.tait_cut)
+    assert hoff[-1] < P["hoff"][-1]              # (an absent pair took entries out)
+    f = np.zeros((g.nall, 3))
+    drho = np.zeros(g.nall)
+    de = np.zeros(g.nall)
+    fn = ref.ref_taitwater_morris if ph.morris else ref.ref_taitwater
+    fn(s.dim, nt, g.nlocal, g.nghost, 1, g.x, P["vest_all"], P["rho_all"], g.type, s.mass,
+       ph.rho0, ph.c0, np.ascontiguousarray(ph.visc), np.ascontiguousarray(ph.tait_cut),
+       hoff, hnb, f, drho, de)
+    fo, dro, deo = po.taitwater(s.dim, g, nt, 1, P["vest_all"], P["rho_all"], s.mass, ph.rho0,
+                                ph.c0, ph.visc, ph.tait_cut, P["hoff"], P["hnb"],
+                                morris=ph.morris)
+    assert np.abs(fo).max() > 0 and np.abs(dro).max() > 0 and np.abs(deo).max() > 0
+    assert np.array_equal(f, fo) and np.array_equal(drho, dro) and np.array_equal(de, deo)
+    hoff, hnb = tu.style_list(g, P["hoff"], P["hnb"], ph.heat_cut)
+    assert hoff[-1] < P["hoff"][-1]
+    de = np.zeros(g.nall)
+    ref.ref_heatconduction(s.dim, nt, g.nlocal, g.nghost, 1, g.x, P["e_all"], P["rho_all"],
+                           g.type, s.mass, np.ascontiguousarray(ph.alpha),
+                           np.ascontiguousarray(ph.heat_cut), hoff, hnb, de)
+    deo = po.heatconduction(s.dim, g, nt, 1, P["e_all"], P["rho_all"], s.mass, ph.alpha,
+                            ph.heat_cut, P["hoff"], P["hnb"])
+    assert np.abs(deo).max() > 0
+    assert np.array_equal(de, deo)
+
+
+@pytest.mark.ref
 @pytest.mark.parametrize("nx,dim", [(10, 3), (16, 2), (7, 3)])
 def test_oracle_vs_reference_lattice_ties(po, ref, nx, dim):
     """On the C5 bubble lattice ~30 pairs per atom sit exactly at the cutoff (skin 0): the
