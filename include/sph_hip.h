@@ -283,7 +283,8 @@ typedef struct {
   double boxlo[3], boxhi[3];   /* global box */
   int periodic[3];
   double skin;                 /* neighbor skin */
-  int neigh_every;             /* rebuild every N steps (neigh_modify every N check no) */
+  int neigh_every;             /* rebuild every N steps (neigh_modify every N delay 0 check no);
+                                  sph_engine_neigh_modify replaces it, with delay and check */
   double dt;                   /* timestep (units lj: ftm2v = 1) */
   double ftm2v;                /* force->ftm2v */
   double mass[SPH_MAXTYPES + 1];
@@ -450,6 +451,28 @@ int sph_engine_phase_change(sph_engine *e, const sph_phasechange_params *p, int 
    sortfreq steps (0 = never).  Default 1000 / 0, LAMMPS' own.  The engine's rows keep their
    own order; only the tracked LAMMPS order changes. */
 int sph_engine_atom_sort(sph_engine *e, int sortfreq, double binsize);
+
+/* neigh_modify every E delay D check yes|no (neighbor.cpp:1332-1347).  Without this call:
+   every = cfg.neigh_every, delay 0, check no -- the engine's behaviour so far.
+   Neighbor::decide per step, after the initial integrate: a due fix phase_change rebuilds
+   first (must_check); otherwise ago (steps since the last build) counts, and a step with
+   ago >= D && ago % E == 0 rebuilds -- with check yes only if an owned atom of any brick has
+   moved more than skin/2 from where the last build left it (|x - xhold|^2 > 0.25 skin^2,
+   strict, fp64).  Only those steps run the checking integrate kernel and read its flag back
+   (one stream synchronise each; bricks take the largest flag, so all rebuild together).
+   Before sph_engine_setup, like sph_engine_idealgas: the setup takes the first hold positions
+   and restarts ago and the counters.
+   SPH_HIP_EINVAL: every <= 0, delay < 0, delay > 0 && delay % every != 0 ("Neighbor delay must
+   be 0 or multiple of every setting", neighbor.cpp:215), check not 0 or 1, after setup. */
+int sph_engine_neigh_modify(sph_engine *e, int every, int delay, int check);
+
+typedef struct {
+  int64_t builds;      /* Neighbor::ncalls: builds since sph_engine_setup, setup's included */
+  int64_t dangerous;   /* Neighbor::ndanger (neighbor.cpp:1408) */
+  int64_t checks;      /* displacement checks evaluated */
+  int64_t last_build;  /* step of the last build */
+} sph_neigh_stats;
+int sph_engine_neigh_stats(sph_engine *e, sph_neigh_stats *out);
 
 /* Static regions (box units), shared by the clamps and the reductions below.  The
    predicates are LAMMPS' own, closed boundaries included: sphere

@@ -97,6 +97,12 @@ class EngineStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class NeighStats(C.Structure):
+    """sph_neigh_stats: Neighbor's build counters since setup."""
+    _fields_ = [("builds", C.c_int64), ("dangerous", C.c_int64), ("checks", C.c_int64),
+                ("last_build", C.c_int64)]
+
+
 SPH_REGION_SPHERE, SPH_REGION_BLOCK = 0, 1
 SPH_SET_RHO, SPH_SET_E, SPH_SET_T, SPH_SET_DE = 0, 1, 2, 3
 SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7)
@@ -299,6 +305,8 @@ EXPORTS = {
     "sph_engine_set_atoms_multiphase": (_i, [_vp, _dp, _vp, _vp]),
     "sph_engine_phase_change": (_i, [_vp, _vp, _i, _i]),
     "sph_engine_atom_sort": (_i, [_vp, _i, C.c_double]),
+    "sph_engine_neigh_modify": (_i, [_vp, _i, _i, _i]),
+    "sph_engine_neigh_stats": (_i, [_vp, C.POINTER(NeighStats)]),
     "sph_engine_get_atoms_multiphase": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sph_engine_write_restart": (_i, [_vp, _vp, C.c_int64, C.POINTER(_i)]),
     "sph_engine_read_restart": (_i, [_vp, _i, _dp]),
@@ -733,6 +741,20 @@ class Engine:
         """atom_modify sort sortfreq binsize: the LAMMPS local order fix phase_change meets its
         candidates in (Atom::sort at setup and every sortfreq steps; 0 = never)."""
         _chk(self.L.sph_engine_atom_sort(self.h, int(sortfreq), float(binsize)))
+
+    def neigh_modify(self, every, delay=0, check=True):
+        """neigh_modify every E delay D check yes|no, before setup(): a step `ago` steps after
+        the last build rebuilds if ago >= delay and ago % every == 0 and -- with check -- an
+        owned atom has moved more than half the skin since that build.  check takes True,
+        False, 1 or 0.  Without this call: every = neigh_every, delay 0, check no."""
+        _chk(self.L.sph_engine_neigh_modify(self.h, int(every), int(delay), int(check)))
+
+    def neigh_stats(self) -> dict:
+        """builds (setup's included), dangerous builds, displacement checks evaluated and the
+        step of the last build, since setup()"""
+        st = NeighStats()
+        _chk(self.L.sph_engine_neigh_stats(self.h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def setmeso(self, what, value, types=None, region=None, noregion=None):
         """fix setmeso meso_rho|meso_e|meso_t value [region|noregion R] / fix setmesode value

@@ -244,6 +244,17 @@ struct sph_engine {
   bool setup_done = false;
   bool global_tags = false;
   int last_build = 0;
+  // Neighbor::decide (neighbor.cpp:1332-1410): steps since the last build, and neigh_modify's
+  // every / delay / check as sph_engine_neigh_modify set them (without the call: every =
+  // cfg.neigh_every, delay 0, check no); the builds, dangerous builds and displacement checks
+  // since setup.  check yes: the owned positions of the last build (xhold), the word the
+  // checking integrate raises and its pinned host copy.
+  bool nm_set = false, nm_check = false;
+  int nm_every = 1, nm_delay = 0;
+  int64_t nm_ago = 0, nm_builds = 0, nm_danger = 0, nm_checks = 0;
+  DBuf<double4> xhold;
+  DBuf<int> nm_flag;
+  int *h_nm = nullptr;
 
   // atoms (owned first, then ghosts): layout of sph_kernels.h
   DBuf<double4> xf, vr;
@@ -1996,6 +2007,40 @@ struct sph_engine {
     build_all(false);
   }
 
+  int neigh_every() const { return nm_set ? nm_every : (cfg.neigh_every > 0 ? cfg.neigh_every : 1); }
+  // Neighbor::decide's test of a step `ago` steps after the last build (neighbor.cpp:1338)
+  bool neigh_eligible(int64_t ago) const { return ago >= nm_delay && ago % neigh_every() == 0; }
+  // After a build (setup's included): ago = 0 and, with check yes, xhold = x of the owned
+  // atoms as the build left them -- wrapped, migrated, sorted (neighbor.cpp:1428-1441); the
+  // rows keep that order until the next build.  The flag is only ever raised by a check that
+  // a build follows, so clearing it here keeps it clear for every check.
+  void neigh_built() {
+    nm_ago = 0;
+    last_build = (int)step;
+    nm_builds++;
+    if (!nm_check) return;
+    xhold.reserve(nlocal > 0 ? nlocal : 1);
+    nm_flag.reserve(1);
+    if (nlocal)
+      SPH_HIP_TRY(hipMemcpyAsync(xhold.p, xf.p, (size_t)nlocal * sizeof(double4),
+                                 hipMemcpyDeviceToDevice, s));
+    SPH_HIP_TRY(hipMemsetAsync(nm_flag.p, 0, sizeof(int), s));
+  }
+  // The check's answer: this brick's flag (one small copy into pinned memory, one stream
+  // synchronise), over bricks the largest (MPI_Allreduce MAX, neighbor.cpp:1407) -- every
+  // rank reaches the same eligible steps, a rank without atoms takes part with 0.
+  bool neigh_flag_any() {
+    SPH_HIP_TRY(hipMemcpyAsync(h_nm, nm_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SPH_HIP_TRY(hipStreamSynchronize(s));
+    int flag = nlocal > 0 ? *h_nm : 0;
+    if (multi() && tr) {
+      std::vector<int> all(tr->size());
+      tr->allgather_int(flag, all.data(), s);
+      flag = *std::max_element(all.begin(), all.end());
+    }
+    return flag != 0;
+  }
+
   void forward() {
     if (multi()) {
       Scope t(this, T_COMM);
@@ -2619,7 +2664,8 @@ struct sph_engine {
       SPH_HIP_TRY(hipMemsetAsync(ff_tot.p, 0, FF_NT * sizeof(double), s));
     }
     post_force_forcefix();  // (FixSetForce::setup / FixAddForce::setup too)
-    last_build = 0;
+    nm_builds = nm_danger = nm_checks = 0;
+    neigh_built();  // (Neighbor::ncalls counts the setup's build)
     setup_done = true;
   }
 
@@ -2630,24 +2676,53 @@ struct sph_engine {
     for (int k = 0; k < nsteps; k++) {
       step++;
       if (sc.x0) sc.moved = moved_flag();
+      // Neighbor::decide (neighbor.cpp:1332-1410).  A due fix phase_change is must_check: it
+      // builds before ago counts.  Otherwise ago counts, and the step is eligible once
+      // ago >= delay && ago % every == 0 -- known before the integrate is launched, so only
+      // an eligible step of a check-yes engine runs the checking instantiation.  (The box
+      // never changes in the engine: the reference's boxcheck branch does not apply.)
+      const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
+      const bool elig = !pc_due && neigh_eligible(nm_ago + 1);
+      const bool chk = elig && nm_check;
       {
         Scope t(this, T_INT);
-        if (k == 0)
-          hipLaunchKernelGGL(k_initial_integrate, dim3(blocks(nlocal)), dim3(BLK), 0, s,
-                             nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
-        else
-          hipLaunchKernelGGL(k_final_initial, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal,
-                             sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
+        if (chk) {
+          const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
+          if (k == 0)
+            hipLaunchKernelGGL(k_initial_integrate<true>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
+                               nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p, nh);
+          else
+            hipLaunchKernelGGL(k_final_initial<true>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
+                               nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p, nh);
+        } else if (k == 0) {
+          hipLaunchKernelGGL(k_initial_integrate<false>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
+                             nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                             NeighHold<false>{});
+        } else {
+          hipLaunchKernelGGL(k_final_initial<false>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
+                             nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                             NeighHold<false>{});
+        }
       }
-      const int every = cfg.neigh_every > 0 ? cfg.neigh_every : 1;
-      const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
+      bool build = pc_due;
+      if (!pc_due) {
+        nm_ago++;
+        if (chk) {
+          nm_checks++;
+          build = neigh_flag_any();
+          // (a check that fires at its first opportunity, neighbor.cpp:1408)
+          if (build && nm_ago == std::max(neigh_every(), nm_delay)) nm_danger++;
+        } else {
+          build = elig;
+        }
+      }
       if (pc_due) {
         phase_change();
         pc_next += pc_nevery;
       }
-      if (pc_due || (step - last_build) % every == 0) {
+      if (build) {
         rebuild();
-        last_build = (int)step;
+        neigh_built();
         pair_compute(rhosum_due());
       } else if (ov_ready && rhosum_due() && overlap_on()) {
         pair_compute_overlap();
@@ -2657,7 +2732,9 @@ struct sph_engine {
       }
       post_force_setmeso();
       post_force_forcefix();
-      refresh_inner(!pc && (step + 1 - last_build) % every == 0);
+      // (check yes: whether the next step rebuilds is not known yet -- a refresh that a
+      // rebuild then supersedes is harmless, the rebuild clears both slots)
+      refresh_inner(nm_check ? (pc && step + 1 == pc_next) : (!pc && neigh_eligible(nm_ago + 1)));
       if (timing && pending.size() > 4096) harvest();
     }
     if (nsteps > 0) {
@@ -2829,6 +2906,7 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
     SPH_HIP_TRY(hipHostMalloc(&e->h_scalar, sizeof(int)));
     SPH_HIP_TRY(hipHostMalloc(&e->h_small, 16 * sizeof(int)));
     SPH_HIP_TRY(hipHostMalloc(&e->h_cs, 2 * sizeof(int)));
+    SPH_HIP_TRY(hipHostMalloc(&e->h_nm, sizeof(int)));
     for (auto &ev : e->cs_ev) SPH_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   } catch (...) {
     delete e;
@@ -2880,11 +2958,14 @@ int sph_engine_destroy(sph_engine *e) {
   for (auto ev : e->cs_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (e->h_cs) (void)hipHostFree(e->h_cs);
+  if (e->h_nm) (void)hipHostFree(e->h_nm);
   for (auto *b : {&e->flags, &e->tmp, &e->cbs, &e->cbr, &e->flag2, &e->fl_in, &e->fl_bd}) b->release();
   e->snbr.release();
   e->snbi.release();
   e->icnt.release();
   e->moved.release();
+  e->xhold.release();
+  e->nm_flag.release();
   e->x0.release();
   e->blen.release();
   for (auto &sw : e->swaps) sw.list.release();
@@ -3437,6 +3518,38 @@ int sph_engine_run(sph_engine *e, int nsteps) {
   SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "sph_engine_run: call sph_engine_setup first");
   SPH_HIP_TRY(hipSetDevice(e->device));
   e->run(nsteps);
+  SPH_API_END
+}
+
+int sph_engine_neigh_modify(sph_engine *e, int every, int delay, int check) {
+  SPH_API_BEGIN
+  // (the arguments first: they are judged the same with or without an engine)
+  SPH_REQUIRE(every > 0 && delay >= 0, SPH_HIP_EINVAL,
+              "sph_engine_neigh_modify: every %d must be positive, delay %d not negative", every,
+              delay);
+  SPH_REQUIRE(delay == 0 || delay % every == 0, SPH_HIP_EINVAL,
+              "Neighbor delay must be 0 or multiple of every setting (every %d delay %d)", every,
+              delay);
+  SPH_REQUIRE(check == 0 || check == 1, SPH_HIP_EINVAL,
+              "sph_engine_neigh_modify: check %d is neither 0 (no) nor 1 (yes)", check);
+  SPH_REQUIRE(e, SPH_HIP_EINVAL, "sph_engine_neigh_modify: NULL engine");
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_neigh_modify: before sph_engine_setup (the setup takes the hold "
+              "positions)");
+  e->nm_set = true;
+  e->nm_every = every;
+  e->nm_delay = delay;
+  e->nm_check = check != 0;
+  SPH_API_END
+}
+
+int sph_engine_neigh_stats(sph_engine *e, sph_neigh_stats *out) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && out, SPH_HIP_EINVAL, "sph_engine_neigh_stats: NULL argument");
+  out->builds = e->nm_builds;
+  out->dangerous = e->nm_danger;
+  out->checks = e->nm_checks;
+  out->last_build = e->last_build;
   SPH_API_END
 }
 

@@ -29,6 +29,38 @@ __device__ __forceinline__ void inner_check(const StepConst &sc, int i, const do
   if (dx * dx + dy * dy + dz * dz > sc.lim2) atomicOr(sc.moved, 1);
 }
 
+// neigh_modify check yes (Neighbor::check_distance, neighbor.cpp:1385-1410): the owned
+// positions held at the last build (xhold, x0's layout: 32 B per atom, two 16-B loads), the
+// trigger 0.25 skin^2 and the word a wave raises once one of its atoms has moved further.
+// Only the CHK instantiations of the integrate kernels carry it: the plain ones take the
+// empty form, so their code is what it was.
+template <bool CHK>
+struct NeighHold {};
+template <>
+struct NeighHold<true> {
+  const double4 *xhold;
+  double trig2;
+  int *flag;
+};
+
+// delx*delx + dely*dely + delz*delz > triggersq in the reference's order (no contraction:
+// every product and sum rounded on its own)
+__device__ __forceinline__ bool neigh_moved(const NeighHold<true> &h, int i, const double4 &x) {
+  const double4 a = h.xhold[i];
+  const double dx = x.x - a.x, dy = x.y - a.y, dz = x.z - a.z;
+  const double rsq = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+  return rsq > h.trig2;
+}
+__device__ __forceinline__ bool neigh_moved(const NeighHold<false> &, int, const double4 &) {
+  return false;
+}
+// one vote per wave, one lane's plain store: the lowest lane that moved writes the flag
+__device__ __forceinline__ void neigh_raise(const NeighHold<true> &h, bool mv) {
+  const unsigned long long b = __ballot(mv);
+  if (b != 0ull && (int)(__lane_id()) == __ffsll((long long)b) - 1) *h.flag = 1;
+}
+__device__ __forceinline__ void neigh_raise(const NeighHold<false> &, bool) {}
+
 // bricks: the ghosts' positions arrive from other ranks, so their displacement since the
 // inner rows were written is checked after each forward comm (one brick: a ghost moves with
 // the owned atom it images, which the integrate kernels check)
@@ -70,15 +102,19 @@ static __global__ void k_x0_cond(int ng, const int *__restrict__ cond,
 }
 
 // FixMeso::initial_integrate (fix_meso.cpp:91-140) / FixMesoStationary (:71-90)
+// CHK (an eligible step of a check-yes engine): the position about to be stored is compared
+// with xhold; stationary types stay where they were held and contribute nothing
+template <bool CHK>
 static __global__ void k_initial_integrate(int n, StepConst sc, double4 *__restrict__ xf,
                                            double4 *__restrict__ vr, double *__restrict__ en,
                                            const int *__restrict__ ty,
                                            double4 *__restrict__ vel,
                                            const double4 *__restrict__ fo,
                                            const double *__restrict__ de,
-                                           const double *__restrict__ rm) {
+                                           const double *__restrict__ rm, NeighHold<CHK> nh) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  bool mv = false;
   const int t = ty[i];
   double4 vv = vr[i];       // vest, rho
   const double4 f = fo[i];  // fx, fy, fz, drho
@@ -100,8 +136,10 @@ static __global__ void k_initial_integrate(int n, StepConst sc, double4 *__restr
     vel[i] = v;
     xf[i] = x;
     inner_check(sc, i, x);
+    if (CHK) mv = neigh_moved(nh, i, x);
   }
   vr[i] = vv;
+  if (CHK) neigh_raise(nh, mv);
 }
 
 // FixMeso::final_integrate (fix_meso.cpp:144-180) / FixMesoStationary (:94-112)
@@ -131,14 +169,16 @@ static __global__ void k_final_integrate(int n, StepConst sc, double4 *__restric
 // between them touches these atoms (Verlet::run: output, then the next step's
 // initial_integrate, verlet.cpp:295-307, 230), so one streaming pass does both with the
 // two kernels' operations in their order (bit-identical results, half the traffic).
+template <bool CHK>
 static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict__ xf,
                                        double4 *__restrict__ vr, double *__restrict__ en,
                                        const int *__restrict__ ty, double4 *__restrict__ vel,
                                        const double4 *__restrict__ fo,
                                        const double *__restrict__ de,
-                                       const double *__restrict__ rm) {
+                                       const double *__restrict__ rm, NeighHold<CHK> nh) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  bool mv = false;
   const int t = ty[i];
   double4 vv = vr[i];
   const double4 f = fo[i];
@@ -167,9 +207,11 @@ static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict_
     vel[i] = v;
     xf[i] = x;
     inner_check(sc, i, x);
+    if (CHK) mv = neigh_moved(nh, i, x);
   }
   en[i] = e;
   vr[i] = vv;
+  if (CHK) neigh_raise(nh, mv);
 }
 
 // FixMeso::setup_pre_force: vest = v (fix_meso.cpp:68-85)
