@@ -474,6 +474,48 @@ typedef struct {
 } sph_neigh_stats;
 int sph_engine_neigh_stats(sph_engine *e, sph_neigh_stats *out);
 
+/* fix ID group dt/reset N tmin tmax xmax units box (fix_dt_reset.cpp).  At setup (after the
+   step-0 forces and the post_force fixes' own setup) and after the final integrate of every
+   step with step % nevery == 0, FixDtReset::end_of_step: per owned atom of the group
+     dtv = xmax / |v|,  dtf = sqrt(2 xmax / (ftm2v |f| / m)),  dt = MIN(dtv, dtf),
+     del = dt v + 0.5 dt^2 f / m ftm2v,  dt *= xmax / |del| if |del| > xmax
+   (BIG = 1e20 for an atom at rest without force; every operation rounded on its own, in the
+   reference's order), the smallest over atoms and bricks, then MAX with tmin, then MIN with
+   tmax.  If that differs from the current dt: Update::update_time, update->dt = dt and
+   FixMeso's dtv = dt, dtf = 0.5 dt ftm2v.  v is the velocity after the final integrate, f the
+   step's force after every post_force fix: the fix acts as one defined after every
+   sph_engine_forcefix and sph_engine_setmeso fix and after cfg.gravity (water_collapse.lmp's
+   order: gfix before dtfix).
+   The scan runs behind the final integrate in one kernel, a one-block kernel folds its
+   per-block minima and keeps dt, {dtv, dtf}, the time and laststep in a device record that
+   the integrate kernels of such an engine read; a reset step cannot fuse its final integrate
+   with the next initial integrate (three launches where other steps have one).  One brick:
+   nothing returns to the host.  Bricks: one stream synchronise per reset step (as
+   neigh_modify check yes has per check) -- the brick's minimum is read back and reduced
+   over the ranks through the transport.
+   Before sph_engine_setup, once.  SPH_HIP_EINVAL: nevery < 1, a negative bound, minbound &&
+   maxbound && tmin >= tmax, xmax <= 0 ("Illegal fix dt/reset command", :52-67); after setup;
+   a second call; together with sph_engine_phase_change in either order (its ENERGY-rate
+   threshold reads update->dt on the host).  Not part of the restart records. */
+typedef struct {
+  int nevery;            /* >= 1 */
+  int minbound; double tmin;   /* minbound 0 = NULL */
+  int maxbound; double tmax;   /* maxbound 0 = NULL */
+  double xmax;           /* box units (the script's `units box`) */
+  int type_mask;         /* the fix's group, as sph_setmeso; 0 = all */
+} sph_dtreset;
+int sph_engine_dt_reset(sph_engine *e, const sph_dtreset *fix);
+
+/* After setup.  Without the fix: cfg.dt, step * cfg.dt, 0, 0.  With it: one small copy and a
+   stream synchronise, as sph_engine_neigh_stats' callers expect of a statistics call. */
+typedef struct {
+  double dt;             /* update->dt now */
+  double time;           /* atime + (step - atimestep) * dt (thermo.cpp:1500) */
+  int64_t laststep;      /* f_dtfix: last step at which dt changed (0 if never) */
+  int64_t changes;       /* how many end_of_step calls changed dt, setup's included */
+} sph_dt_stats;
+int sph_engine_dt_stats(sph_engine *e, sph_dt_stats *out);
+
 /* Static regions (box units), shared by the clamps and the reductions below.  The
    predicates are LAMMPS' own, closed boundaries included: sphere
    sqrt(dx*dx+dy*dy+dz*dz) <= radius (region_sphere.cpp:96-105), block x >= xlo && x <= xhi

@@ -103,6 +103,19 @@ class NeighStats(C.Structure):
                 ("last_build", C.c_int64)]
 
 
+class DtReset(C.Structure):
+    """sph_dtreset: fix dt/reset N tmin tmax xmax units box"""
+    _fields_ = [("nevery", C.c_int), ("minbound", C.c_int), ("tmin", C.c_double),
+                ("maxbound", C.c_int), ("tmax", C.c_double), ("xmax", C.c_double),
+                ("type_mask", C.c_int)]
+
+
+class DtStats(C.Structure):
+    """sph_dt_stats: update->dt, thermo's time, f_dtfix and the number of changes"""
+    _fields_ = [("dt", C.c_double), ("time", C.c_double), ("laststep", C.c_int64),
+                ("changes", C.c_int64)]
+
+
 SPH_REGION_SPHERE, SPH_REGION_BLOCK = 0, 1
 SPH_SET_RHO, SPH_SET_E, SPH_SET_T, SPH_SET_DE = 0, 1, 2, 3
 SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7)
@@ -307,6 +320,8 @@ EXPORTS = {
     "sph_engine_atom_sort": (_i, [_vp, _i, C.c_double]),
     "sph_engine_neigh_modify": (_i, [_vp, _i, _i, _i]),
     "sph_engine_neigh_stats": (_i, [_vp, C.POINTER(NeighStats)]),
+    "sph_engine_dt_reset": (_i, [_vp, C.POINTER(DtReset)]),
+    "sph_engine_dt_stats": (_i, [_vp, C.POINTER(DtStats)]),
     "sph_engine_get_atoms_multiphase": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sph_engine_write_restart": (_i, [_vp, _vp, C.c_int64, C.POINTER(_i)]),
     "sph_engine_read_restart": (_i, [_vp, _i, _dp]),
@@ -755,6 +770,26 @@ class Engine:
         st = NeighStats()
         _chk(self.L.sph_engine_neigh_stats(self.h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def dt_reset(self, nevery, tmin, tmax, xmax, type_mask=0):
+        """fix dt/reset nevery tmin tmax xmax units box on the group of type_mask (bit t = type
+        t, 0 = all), before setup(), once: at setup and after every nevery-th step dt becomes
+        the smallest per-atom step that moves no atom of the group further than xmax, bounded
+        by tmin and tmax (None = NULL).  It reads the force after every setforce / addforce /
+        setmeso fix and gravity.  Not together with phase_change."""
+        fx = DtReset(int(nevery), int(tmin is not None), 0.0 if tmin is None else float(tmin),
+                     int(tmax is not None), 0.0 if tmax is None else float(tmax), float(xmax),
+                     int(type_mask))
+        _chk(self.L.sph_engine_dt_reset(self.h, C.byref(fx)))
+
+    def dt_stats(self) -> dict:
+        """dt (update->dt now), time (thermo's), laststep (f_dtfix: the last step at which dt
+        changed) and changes (end_of_step calls that changed dt), after setup(); an engine
+        without dt_reset reports its fixed dt, step * dt, 0 and 0"""
+        st = DtStats()
+        _chk(self.L.sph_engine_dt_stats(self.h, C.byref(st)))
+        return dict(dt=float(st.dt), time=float(st.time), laststep=int(st.laststep),
+                    changes=int(st.changes))
 
     def setmeso(self, what, value, types=None, region=None, noregion=None):
         """fix setmeso meso_rho|meso_e|meso_t value [region|noregion R] / fix setmesode value

@@ -255,6 +255,17 @@ struct sph_engine {
   DBuf<double4> xhold;
   DBuf<int> nm_flag;
   int *h_nm = nullptr;
+  // fix dt/reset (sph_engine_dt_reset; fix_dt_reset.cpp): the fix as armed, the device record
+  // its fold keeps (dt, {dtv, dtf}, time, laststep: sph_engine_kernels.h DtRecord), one
+  // partial per block of the scan, and the record's pinned host copy (sph_engine_dt_stats,
+  // and the bricks' minimum).  The fix acts as one defined after every forcefix / setmeso fix
+  // and after cfg.gravity: it reads the step's force after all of them.
+  bool dtr_on = false;
+  int dtr_nevery = 1;
+  DtFix dtr{};
+  DBuf<DtRecord> dt_rec;
+  DBuf<double> dt_part;
+  DtRecord *h_dt = nullptr;
 
   // atoms (owned first, then ghosts): layout of sph_kernels.h
   DBuf<double4> xf, vr;
@@ -2041,6 +2052,62 @@ struct sph_engine {
     return flag != 0;
   }
 
+  // FixDtReset::init at setup: the record starts from cfg.dt at time 0, laststep 0
+  void dt_reset_init() {
+    dt_rec.reserve(1);
+    DtRecord r{};
+    r.dt = r.dtv = cfg.dt;
+    r.dtf = sc.dtf;
+    r.brick_min = DT_BIG;
+    *h_dt = r;
+    SPH_HIP_TRY(hipMemcpyAsync(dt_rec.p, h_dt, sizeof(DtRecord), hipMemcpyHostToDevice, s));
+    SPH_HIP_TRY(hipStreamSynchronize(s));  // (h_dt is read back into later)
+  }
+  // FixDtReset::end_of_step (fix_dt_reset.cpp:131-186) of the current step: the scan over the
+  // owned atoms -- with_final: behind FixMeso::final_integrate in the same pass -- and the
+  // one-block fold.  One brick: two launches, nothing returns to the host.  Bricks: the fold
+  // leaves this brick's minimum in the record; the host reads it back (one stream synchronise
+  // per reset step, as neigh_flag_any has per check), takes the smallest over the ranks
+  // (MPI_Allreduce MIN, :168; a rank without atoms takes part with BIG) and launches the
+  // bounds-and-apply part with it.  The bit pattern of a positive double orders as an
+  // unsigned 64-bit integer, so it travels as two allgather_int words.
+  void dt_end_of_step(bool with_final) {
+    Scope t(this, T_INT);
+    const unsigned nb = blocks(nlocal);
+    dt_part.reserve(nb > 0 ? nb : 1);
+    const double *m = rm.p;
+    if (nb) {
+      if (with_final)
+        hipLaunchKernelGGL(k_dt_scan<true>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr, dt_rec.p,
+                           vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
+      else
+        hipLaunchKernelGGL(k_dt_scan<false>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr,
+                           dt_rec.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
+    }
+    if (!(multi() && tr)) {
+      hipLaunchKernelGGL(k_dt_fold<false>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
+                         (long long)step, dt_rec.p);
+      return;
+    }
+    hipLaunchKernelGGL(k_dt_fold<true>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
+                       (long long)step, dt_rec.p);
+    SPH_HIP_TRY(hipMemcpyAsync(h_dt, dt_rec.p, sizeof(DtRecord), hipMemcpyDeviceToHost, s));
+    SPH_HIP_TRY(hipStreamSynchronize(s));
+    uint64_t bits;
+    std::memcpy(&bits, &h_dt->brick_min, sizeof bits);
+    std::vector<int> hi(tr->size()), lo(tr->size());
+    tr->allgather_int((int)(uint32_t)(bits >> 32), hi.data(), s);
+    tr->allgather_int((int)(uint32_t)(bits & 0xffffffffu), lo.data(), s);
+    for (int r = 0; r < tr->size(); r++) {
+      const uint64_t b = ((uint64_t)(uint32_t)hi[r] << 32) | (uint64_t)(uint32_t)lo[r];
+      bits = std::min(bits, b);
+    }
+    double dtmin;
+    std::memcpy(&dtmin, &bits, sizeof dtmin);
+    hipLaunchKernelGGL(k_dt_apply, dim3(1), dim3(64), 0, s, dtmin, dtr, (long long)step,
+                       dt_rec.p);
+  }
+
   void forward() {
     if (multi()) {
       Scope t(this, T_COMM);
@@ -2666,13 +2733,42 @@ struct sph_engine {
     post_force_forcefix();  // (FixSetForce::setup / FixAddForce::setup too)
     nm_builds = nm_danger = nm_checks = 0;
     neigh_built();  // (Neighbor::ncalls counts the setup's build)
+    if (dtr_on) {  // FixDtReset::setup = end_of_step, after every post_force fix's own setup
+      dt_reset_init();
+      dt_end_of_step(false);
+    }
     setup_done = true;
+  }
+
+  // The step's integrate launch of an engine with fix dt/reset: the same kernels in their
+  // instantiations that take {dtv, dtf} from the device record.  alone: the previous step's
+  // final integrate has run already (the first step of a run, or the step after a reset step).
+  void integrate_dt(bool alone, bool chk) {
+    Scope t(this, T_INT);
+    const DtFrom<true> dr{&dt_rec.p->dtv};
+    const dim3 g(blocks(nlocal)), b(BLK);
+    if (chk) {
+      const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
+      if (alone)
+        hipLaunchKernelGGL((k_initial_integrate<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                           en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
+      else
+        hipLaunchKernelGGL((k_final_initial<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                           en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
+    } else if (alone) {
+      hipLaunchKernelGGL((k_initial_integrate<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                         en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
+    } else {
+      hipLaunchKernelGGL((k_final_initial<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p, en.p,
+                         ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
+    }
   }
 
   // Verlet::run (verlet.cpp:222-308)
   void run(int nsteps) {
     // the final_integrate of step k-1 runs fused with the initial_integrate of step k;
     // the last step's final_integrate runs on its own after the loop
+    bool final_done = false;  // (fix dt/reset: the step's final integrate has run already)
     for (int k = 0; k < nsteps; k++) {
       step++;
       if (sc.x0) sc.moved = moved_flag();
@@ -2684,24 +2780,28 @@ struct sph_engine {
       const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
       const bool elig = !pc_due && neigh_eligible(nm_ago + 1);
       const bool chk = elig && nm_check;
-      {
+      if (dtr_on) {
+        integrate_dt(k == 0 || final_done, chk);
+      } else {
         Scope t(this, T_INT);
         if (chk) {
           const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
           if (k == 0)
-            hipLaunchKernelGGL(k_initial_integrate<true>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
-                               nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p, nh);
+            hipLaunchKernelGGL((k_initial_integrate<true, false>), dim3(blocks(nlocal)), dim3(BLK),
+                               0, s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                               StepOpt<true, false>{nh});
           else
-            hipLaunchKernelGGL(k_final_initial<true>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
-                               nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p, nh);
+            hipLaunchKernelGGL((k_final_initial<true, false>), dim3(blocks(nlocal)), dim3(BLK), 0,
+                               s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                               StepOpt<true, false>{nh});
         } else if (k == 0) {
-          hipLaunchKernelGGL(k_initial_integrate<false>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
-                             nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                             NeighHold<false>{});
+          hipLaunchKernelGGL((k_initial_integrate<false, false>), dim3(blocks(nlocal)), dim3(BLK),
+                             0, s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                             StepOpt<false, false>{});
         } else {
-          hipLaunchKernelGGL(k_final_initial<false>, dim3(blocks(nlocal)), dim3(BLK), 0, s,
-                             nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                             NeighHold<false>{});
+          hipLaunchKernelGGL((k_final_initial<false, false>), dim3(blocks(nlocal)), dim3(BLK), 0,
+                             s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                             StepOpt<false, false>{});
         }
       }
       bool build = pc_due;
@@ -2736,11 +2836,23 @@ struct sph_engine {
       // rebuild then supersedes is harmless, the rebuild clears both slots)
       refresh_inner(nm_check ? (pc && step + 1 == pc_next) : (!pc && neigh_eligible(nm_ago + 1)));
       if (timing && pending.size() > 4096) harvest();
+      // fix dt/reset: Modify::end_of_step follows the final integrate of a step with
+      // ntimestep % nevery == 0 (modify.cpp:404-408, verlet.cpp:299), and the next initial
+      // integrate needs the dt it leaves: the final integrate runs here with the scan behind
+      // it, then the fold, and the next step (or the next run) integrates on its own -- three
+      // launches where the other steps have the fused one
+      final_done = dtr_on && step % dtr_nevery == 0;
+      if (final_done) dt_end_of_step(true);
     }
-    if (nsteps > 0) {
+    if (nsteps > 0 && !final_done) {
       Scope t(this, T_INT);
-      hipLaunchKernelGGL(k_final_integrate, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, sc,
-                         vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
+      if (dtr_on)
+        hipLaunchKernelGGL(k_final_integrate_dt, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal,
+                           sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+                           DtFrom<true>{&dt_rec.p->dtv});
+      else
+        hipLaunchKernelGGL(k_final_integrate, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, sc,
+                           vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
     }
     SPH_HIP_TRY(hipGetLastError());
   }
@@ -2907,6 +3019,7 @@ int sph_engine_create(int device, const sph_engine_config *cfg, sph_engine **out
     SPH_HIP_TRY(hipHostMalloc(&e->h_small, 16 * sizeof(int)));
     SPH_HIP_TRY(hipHostMalloc(&e->h_cs, 2 * sizeof(int)));
     SPH_HIP_TRY(hipHostMalloc(&e->h_nm, sizeof(int)));
+    SPH_HIP_TRY(hipHostMalloc(&e->h_dt, sizeof(DtRecord)));
     for (auto &ev : e->cs_ev) SPH_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   } catch (...) {
     delete e;
@@ -2959,6 +3072,9 @@ int sph_engine_destroy(sph_engine *e) {
     if (ev) (void)hipEventDestroy(ev);
   if (e->h_cs) (void)hipHostFree(e->h_cs);
   if (e->h_nm) (void)hipHostFree(e->h_nm);
+  if (e->h_dt) (void)hipHostFree(e->h_dt);
+  e->dt_rec.release();
+  e->dt_part.release();
   for (auto *b : {&e->flags, &e->tmp, &e->cbs, &e->cbr, &e->flag2, &e->fl_in, &e->fl_bd}) b->release();
   e->snbr.release();
   e->snbi.release();
@@ -3085,6 +3201,9 @@ int sph_engine_phase_change(sph_engine *e, const sph_phasechange_params *p, int 
   SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
               "sph_engine_phase_change: arm the fix before sph_engine_setup (its local-order "
               "bookkeeping starts at set_atoms)");
+  SPH_REQUIRE(!e->dtr_on, SPH_HIP_EINVAL,
+              "sph_engine_phase_change: not together with sph_engine_dt_reset (the fix's "
+              "ENERGY-rate threshold reads update->dt, which then lives on the device)");
   SPH_REQUIRE(nevery >= 1, SPH_HIP_EINVAL, "sph_engine_phase_change: nevery < 1");
   SPH_REQUIRE(p->to_mass > 0.0 && p->maxattempt >= 1 && p->cutoff > 0.0, SPH_HIP_EINVAL,
               "sph_engine_phase_change: bad parameters");
@@ -3550,6 +3669,62 @@ int sph_engine_neigh_stats(sph_engine *e, sph_neigh_stats *out) {
   out->dangerous = e->nm_danger;
   out->checks = e->nm_checks;
   out->last_build = e->last_build;
+  SPH_API_END
+}
+
+int sph_engine_dt_reset(sph_engine *e, const sph_dtreset *fix) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && fix, SPH_HIP_EINVAL, "sph_engine_dt_reset: NULL argument");
+  // "Illegal fix dt/reset command" (fix_dt_reset.cpp:52-67)
+  SPH_REQUIRE(fix->nevery >= 1, SPH_HIP_EINVAL, "sph_engine_dt_reset: nevery %d < 1",
+              fix->nevery);
+  SPH_REQUIRE(!(fix->minbound && fix->tmin < 0.0) && !(fix->maxbound && fix->tmax < 0.0),
+              SPH_HIP_EINVAL, "sph_engine_dt_reset: a negative bound (tmin %g, tmax %g)",
+              fix->tmin, fix->tmax);
+  SPH_REQUIRE(!(fix->minbound && fix->maxbound && fix->tmin >= fix->tmax), SPH_HIP_EINVAL,
+              "sph_engine_dt_reset: tmin %g >= tmax %g", fix->tmin, fix->tmax);
+  SPH_REQUIRE(fix->xmax > 0.0, SPH_HIP_EINVAL, "sph_engine_dt_reset: xmax %g <= 0", fix->xmax);
+  SPH_REQUIRE(fix->type_mask >= 0, SPH_HIP_EINVAL, "sph_engine_dt_reset: type_mask %d",
+              fix->type_mask);
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_dt_reset: before sph_engine_setup (the setup runs the fix's first "
+              "end_of_step)");
+  SPH_REQUIRE(!e->dtr_on, SPH_HIP_EINVAL, "sph_engine_dt_reset: the fix is armed already");
+  SPH_REQUIRE(!e->pc, SPH_HIP_EINVAL,
+              "sph_engine_dt_reset: not together with sph_engine_phase_change (the fix's "
+              "ENERGY-rate threshold reads update->dt, which then lives on the device)");
+  e->dtr_on = true;
+  e->dtr_nevery = fix->nevery;
+  e->dtr.minbound = fix->minbound != 0;
+  e->dtr.maxbound = fix->maxbound != 0;
+  e->dtr.tmin = fix->tmin;
+  e->dtr.tmax = fix->tmax;
+  e->dtr.xmax = fix->xmax;
+  e->dtr.ftm2v = e->cfg.ftm2v > 0 ? e->cfg.ftm2v : 1.0;
+  e->dtr.type_mask = fix->type_mask;
+  SPH_API_END
+}
+
+int sph_engine_dt_stats(sph_engine *e, sph_dt_stats *out) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && out, SPH_HIP_EINVAL, "sph_engine_dt_stats: NULL argument");
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "sph_engine_dt_stats: after sph_engine_setup");
+  if (!e->dtr_on) {
+    out->dt = e->cfg.dt;
+    out->time = (double)e->step * e->cfg.dt;
+    out->laststep = out->changes = 0;
+  } else {
+    SPH_HIP_TRY(hipSetDevice(e->device));
+    SPH_HIP_TRY(hipMemcpyAsync(e->h_dt, e->dt_rec.p, sizeof(DtRecord), hipMemcpyDeviceToHost,
+                               e->s));
+    SPH_HIP_TRY(hipStreamSynchronize(e->s));
+    const DtRecord &r = *e->h_dt;
+    out->dt = r.dt;
+    // Thermo's time (thermo.cpp:1500)
+    out->time = r.atime + (double)((long long)e->step - r.atimestep) * r.dt;
+    out->laststep = r.laststep;
+    out->changes = r.changes;
+  }
   SPH_API_END
 }
 

@@ -61,6 +61,34 @@ __device__ __forceinline__ void neigh_raise(const NeighHold<true> &h, bool mv) {
 }
 __device__ __forceinline__ void neigh_raise(const NeighHold<false> &, bool) {}
 
+// fix dt/reset: the integrate kernels of an engine with the fix armed take FixMeso's
+// {dtv, dtf} from the device record the fold kernel keeps (DtRecord below: its first two
+// doubles), not from StepConst -- a load of two doubles that is uniform across the wave.
+// Only the DTR instantiations carry the pointer: the plain ones take the empty form and read
+// sc, so their code is what it was.
+template <bool DTR>
+struct DtFrom {};
+template <>
+struct DtFrom<true> {
+  const double *rec;   // {dtv, dtf}
+};
+__device__ __forceinline__ double step_dtv(const StepConst &sc, const DtFrom<false> &) {
+  return sc.dtv;
+}
+__device__ __forceinline__ double step_dtf(const StepConst &sc, const DtFrom<false> &) {
+  return sc.dtf;
+}
+__device__ __forceinline__ double step_dtv(const StepConst &, const DtFrom<true> &d) {
+  return d.rec[0];
+}
+__device__ __forceinline__ double step_dtf(const StepConst &, const DtFrom<true> &d) {
+  return d.rec[1];
+}
+// what an integrate kernel takes beside its arrays: both parts empty in the plain
+// instantiations (one empty kernel argument, as NeighHold<false> alone was)
+template <bool CHK, bool DTR>
+struct StepOpt : NeighHold<CHK>, DtFrom<DTR> {};
+
 // bricks: the ghosts' positions arrive from other ranks, so their displacement since the
 // inner rows were written is checked after each forward comm (one brick: a ghost moves with
 // the owned atom it images, which the integrate kernels check)
@@ -104,35 +132,36 @@ static __global__ void k_x0_cond(int ng, const int *__restrict__ cond,
 // FixMeso::initial_integrate (fix_meso.cpp:91-140) / FixMesoStationary (:71-90)
 // CHK (an eligible step of a check-yes engine): the position about to be stored is compared
 // with xhold; stationary types stay where they were held and contribute nothing
-template <bool CHK>
+// DTR (an engine with fix dt/reset): dtv and dtf come from the device record
+template <bool CHK, bool DTR>
 static __global__ void k_initial_integrate(int n, StepConst sc, double4 *__restrict__ xf,
                                            double4 *__restrict__ vr, double *__restrict__ en,
                                            const int *__restrict__ ty,
                                            double4 *__restrict__ vel,
                                            const double4 *__restrict__ fo,
                                            const double *__restrict__ de,
-                                           const double *__restrict__ rm, NeighHold<CHK> nh) {
+                                           const double *__restrict__ rm, StepOpt<CHK, DTR> nh) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool mv = false;
   const int t = ty[i];
   double4 vv = vr[i];       // vest, rho
   const double4 f = fo[i];  // fx, fy, fz, drho
-  en[i] += sc.dtf * de[i];
-  vv.w += sc.dtf * f.w;
+  en[i] += step_dtf(sc, nh) * de[i];
+  vv.w += step_dtf(sc, nh) * f.w;
   if (!((sc.stationary_mask >> t) & 1)) {
     double4 x = xf[i];
     double4 v = vel[i];
-    const double dtfm = sc.dtf / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
+    const double dtfm = step_dtf(sc, nh) / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
     vv.x = v.x + 2.0 * dtfm * f.x;
     vv.y = v.y + 2.0 * dtfm * f.y;
     vv.z = v.z + 2.0 * dtfm * f.z;
     v.x += dtfm * f.x;
     v.y += dtfm * f.y;
     v.z += dtfm * f.z;
-    x.x += sc.dtv * v.x;
-    x.y += sc.dtv * v.y;
-    x.z += sc.dtv * v.z;
+    x.x += step_dtv(sc, nh) * v.x;
+    x.y += step_dtv(sc, nh) * v.y;
+    x.z += step_dtv(sc, nh) * v.z;
     vel[i] = v;
     xf[i] = x;
     inner_check(sc, i, x);
@@ -143,39 +172,61 @@ static __global__ void k_initial_integrate(int n, StepConst sc, double4 *__restr
 }
 
 // FixMeso::final_integrate (fix_meso.cpp:144-180) / FixMesoStationary (:94-112)
-static __global__ void k_final_integrate(int n, StepConst sc, double4 *__restrict__ vr,
-                                         double *__restrict__ en, const int *__restrict__ ty,
-                                         double4 *__restrict__ vel,
-                                         const double4 *__restrict__ fo,
-                                         const double *__restrict__ de,
-                                         const double *__restrict__ rm) {
+template <bool DTR>
+__device__ __forceinline__ void final_integrate(int n, const StepConst &sc,
+                                                double4 *__restrict__ vr,
+                                                double *__restrict__ en,
+                                                const int *__restrict__ ty,
+                                                double4 *__restrict__ vel,
+                                                const double4 *__restrict__ fo,
+                                                const double *__restrict__ de,
+                                                const double *__restrict__ rm,
+                                                const DtFrom<DTR> &dr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int t = ty[i];
   const double4 f = fo[i];
   if (!((sc.stationary_mask >> t) & 1)) {
     double4 v = vel[i];
-    const double dtfm = sc.dtf / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
+    const double dtfm = step_dtf(sc, dr) / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
     v.x += dtfm * f.x;
     v.y += dtfm * f.y;
     v.z += dtfm * f.z;
     vel[i] = v;
   }
-  en[i] += sc.dtf * de[i];
-  vr[i].w += sc.dtf * f.w;
+  en[i] += step_dtf(sc, dr) * de[i];
+  vr[i].w += step_dtf(sc, dr) * f.w;
+}
+static __global__ void k_final_integrate(int n, StepConst sc, double4 *__restrict__ vr,
+                                         double *__restrict__ en, const int *__restrict__ ty,
+                                         double4 *__restrict__ vel,
+                                         const double4 *__restrict__ fo,
+                                         const double *__restrict__ de,
+                                         const double *__restrict__ rm) {
+  final_integrate(n, sc, vr, en, ty, vel, fo, de, rm, DtFrom<false>{});
+}
+// ... of an engine with fix dt/reset, on a step that is not a reset step
+static __global__ void k_final_integrate_dt(int n, StepConst sc, double4 *__restrict__ vr,
+                                            double *__restrict__ en,
+                                            const int *__restrict__ ty,
+                                            double4 *__restrict__ vel,
+                                            const double4 *__restrict__ fo,
+                                            const double *__restrict__ de,
+                                            const double *__restrict__ rm, DtFrom<true> dr) {
+  final_integrate(n, sc, vr, en, ty, vel, fo, de, rm, dr);
 }
 
 // FixMeso::final_integrate of one step fused with initial_integrate of the next: nothing
 // between them touches these atoms (Verlet::run: output, then the next step's
 // initial_integrate, verlet.cpp:295-307, 230), so one streaming pass does both with the
 // two kernels' operations in their order (bit-identical results, half the traffic).
-template <bool CHK>
+template <bool CHK, bool DTR>
 static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict__ xf,
                                        double4 *__restrict__ vr, double *__restrict__ en,
                                        const int *__restrict__ ty, double4 *__restrict__ vel,
                                        const double4 *__restrict__ fo,
                                        const double *__restrict__ de,
-                                       const double *__restrict__ rm, NeighHold<CHK> nh) {
+                                       const double *__restrict__ rm, StepOpt<CHK, DTR> nh) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool mv = false;
@@ -184,14 +235,14 @@ static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict_
   const double4 f = fo[i];
   const double dei = de[i];
   double e = en[i];
-  e += sc.dtf * dei;        // final
-  vv.w += sc.dtf * f.w;
-  e += sc.dtf * dei;        // initial
-  vv.w += sc.dtf * f.w;
+  e += step_dtf(sc, nh) * dei;           // final
+  vv.w += step_dtf(sc, nh) * f.w;
+  e += step_dtf(sc, nh) * dei;           // initial
+  vv.w += step_dtf(sc, nh) * f.w;
   if (!((sc.stationary_mask >> t) & 1)) {
     double4 x = xf[i];
     double4 v = vel[i];
-    const double dtfm = sc.dtf / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
+    const double dtfm = step_dtf(sc, nh) / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
     v.x += dtfm * f.x;      // final
     v.y += dtfm * f.y;
     v.z += dtfm * f.z;
@@ -201,9 +252,9 @@ static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict_
     v.x += dtfm * f.x;
     v.y += dtfm * f.y;
     v.z += dtfm * f.z;
-    x.x += sc.dtv * v.x;
-    x.y += sc.dtv * v.y;
-    x.z += sc.dtv * v.z;
+    x.x += step_dtv(sc, nh) * v.x;
+    x.y += step_dtv(sc, nh) * v.y;
+    x.z += step_dtv(sc, nh) * v.z;
     vel[i] = v;
     xf[i] = x;
     inner_check(sc, i, x);
@@ -212,6 +263,146 @@ static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict_
   en[i] = e;
   vr[i] = vv;
   if (CHK) neigh_raise(nh, mv);
+}
+
+// ---- fix dt/reset (fix_dt_reset.cpp:131-186) ---------------------------------------------
+// The fix as armed (sph_engine_dt_reset) and the record the fold keeps on the device: FixMeso's
+// {dtv, dtf} first (DtFrom<true> reads them), update->dt, Update::update_time's atime /
+// atimestep (update.cpp:482-483), the fix's laststep (f_dtfix), how many end_of_step calls
+// changed dt, and -- bricks -- this brick's minimum before the bounds.
+struct DtFix {
+  int minbound, maxbound;
+  double tmin, tmax, xmax, ftm2v;
+  int type_mask;
+};
+struct DtRecord {
+  double dtv, dtf;
+  double dt, atime;
+  long long atimestep, laststep, changes;
+  double brick_min;
+};
+constexpr double DT_BIG = 1.0e20;   // fix_dt_reset.cpp:33
+
+// One atom's dt (fix_dt_reset.cpp:151-164), every product, sum, quotient and square root
+// rounded on its own and taken left to right as the reference writes them: no contraction in
+// this function, so the result is the double the reference computes from the same v and f.
+__device__ __forceinline__ double dt_reset_atom(double vx, double vy, double vz, double fx,
+                                                double fy, double fz, double m, double xmax,
+                                                double ftm2v) {
+#pragma clang fp contract(off)
+  const double massinv = 1.0 / m;
+  const double vsq = vx * vx + vy * vy + vz * vz;
+  const double fsq = fx * fx + fy * fy + fz * fz;
+  double dtv = DT_BIG, dtf = DT_BIG;
+  if (vsq > 0.0) dtv = xmax / __builtin_sqrt(vsq);
+  if (fsq > 0.0) dtf = __builtin_sqrt(2.0 * xmax / (ftm2v * __builtin_sqrt(fsq) * massinv));
+  double dt = dtv < dtf ? dtv : dtf;
+  const double dtsq = dt * dt;
+  const double delx = dt * vx + 0.5 * dtsq * massinv * fx * ftm2v;
+  const double dely = dt * vy + 0.5 * dtsq * massinv * fy * ftm2v;
+  const double delz = dt * vz + 0.5 * dtsq * massinv * fz * ftm2v;
+  const double delr = __builtin_sqrt(delx * delx + dely * dely + delz * delz);
+  if (delr > xmax) dt *= xmax / delr;
+  return dt;
+}
+
+// the smallest value of a wave64, in every lane (xor butterfly: six cross-lane steps)
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+// ... and of a block of up to 16 waves, in thread 0 (one LDS word per wave)
+__device__ __forceinline__ double block_min(double v, double *lds) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  v = wave_min(v);
+  if (lane == 0) lds[w] = v;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int k = 1; k < nw; k++) v = lds[k] < v ? lds[k] : v;
+  return v;
+}
+
+// FixMeso::final_integrate (INT: k_final_integrate's body with dtf from the record) followed
+// by FixDtReset::end_of_step's loop over the owned atoms: the velocity just written and the
+// force in registers give the atom's dt; atoms outside the group and the tail lanes of the
+// last block contribute BIG; one partial per block.  Stationary types are not integrated but
+// are in the group if the mask says so (their v as it stands).  INT = false: the scan alone,
+// for FixDtReset::setup.
+template <bool INT>
+static __global__ void k_dt_scan(int n, StepConst sc, DtFix fx, const DtRecord *__restrict__ rec,
+                                 double4 *__restrict__ vr, double *__restrict__ en,
+                                 const int *__restrict__ ty, double4 *__restrict__ vel,
+                                 const double4 *__restrict__ fo, const double *__restrict__ de,
+                                 const double *__restrict__ rm, double *__restrict__ part) {
+  __shared__ double lds[16];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double dt = DT_BIG;
+  if (i < n) {
+    const int t = ty[i];
+    const double4 f = fo[i];
+    double4 v = vel[i];
+    const double m = rm ? rm[i] : sc.mass[t];  // rmass if per-atom
+    if (INT) {
+      const double dtf = rec->dtf;
+      if (!((sc.stationary_mask >> t) & 1)) {
+        const double dtfm = dtf / m;
+        v.x += dtfm * f.x;
+        v.y += dtfm * f.y;
+        v.z += dtfm * f.z;
+        vel[i] = v;
+      }
+      en[i] += dtf * de[i];
+      vr[i].w += dtf * f.w;
+    }
+    if (fx.type_mask == 0 || ((fx.type_mask >> t) & 1))
+      dt = dt_reset_atom(v.x, v.y, v.z, f.x, f.y, f.z, m, fx.xmax, fx.ftm2v);
+  }
+  dt = block_min(dt, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = dt;
+}
+
+// The rest of end_of_step (fix_dt_reset.cpp:170-185), by one lane: the bounds, MAX with tmin
+// first, then MIN with tmax; an unchanged dt changes nothing; otherwise update_time, the new
+// dt and every fix's reset_dt (fix_meso.cpp:184-187).
+__device__ __forceinline__ void dt_apply(double dt, const DtFix &fx, long long step,
+                                         DtRecord *rec) {
+#pragma clang fp contract(off)
+  if (fx.minbound) dt = dt > fx.tmin ? dt : fx.tmin;
+  if (fx.maxbound) dt = dt < fx.tmax ? dt : fx.tmax;
+  const double old = rec->dt;
+  if (dt == old) return;
+  rec->atime = rec->atime + (double)(step - rec->atimestep) * old;
+  rec->atimestep = step;
+  rec->laststep = step;
+  rec->changes = rec->changes + 1;
+  rec->dt = dt;
+  rec->dtv = dt;
+  rec->dtf = 0.5 * dt * fx.ftm2v;
+}
+
+// One block folds the partials.  One brick: the bounds and the change are applied here and
+// nothing returns to the host.  Bricks (BRICK): the minimum before the bounds goes into the
+// record for the host to reduce over the ranks; k_dt_apply follows with the world's value.
+template <bool BRICK>
+static __global__ void k_dt_fold(int nb, const double *__restrict__ part, DtFix fx,
+                                 long long step, DtRecord *__restrict__ rec) {
+  __shared__ double lds[16];
+  double dt = DT_BIG;
+  for (int k = threadIdx.x; k < nb; k += blockDim.x) dt = part[k] < dt ? part[k] : dt;
+  dt = block_min(dt, lds);
+  if (threadIdx.x != 0) return;
+  if (BRICK)
+    rec->brick_min = dt;
+  else
+    dt_apply(dt, fx, step, rec);
+}
+static __global__ void k_dt_apply(double dt, DtFix fx, long long step,
+                                  DtRecord *__restrict__ rec) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) dt_apply(dt, fx, step, rec);
 }
 
 // FixMeso::setup_pre_force: vest = v (fix_meso.cpp:68-85)
