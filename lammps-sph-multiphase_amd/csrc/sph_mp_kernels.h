@@ -83,22 +83,28 @@ __device__ __forceinline__ double mp_rcp(double b) {
 // evaluated correctly rounded (double-double products, one final rounding): glibc's pow
 // agrees with the correctly rounded power except in ~0.08 % of calls (1 ulp, tools/
 // quintic_pow_check.c), so dW matches the reference bit for bit except there.
+// (contraction off: fusing p + fma(x, l, e) into fma(x, h, ...) would add the residual e of
+// x * h a second time, and the result is then up to an ulp off)
 __device__ __forceinline__ double qr_pow3(double x) {  // x^3, correctly rounded
+#pragma clang fp contract(off)
   const double h = x * x, l = fma(x, x, -h);
   const double p = x * h, e = fma(x, h, -p);
   return p + fma(x, l, e);
 }
 __device__ __forceinline__ void qr_pow4dd(double x, double &q, double &t) {  // x^4 = q + t
+#pragma clang fp contract(off)
   const double h = x * x, l = fma(x, x, -h);
   q = h * h;
   t = fma(2.0 * h, l, fma(h, h, -q));
 }
 __device__ __forceinline__ double qr_pow4(double x) {
+#pragma clang fp contract(off)
   double q, t;
   qr_pow4dd(x, q, t);
   return q + t;
 }
 __device__ __forceinline__ double qr_pow5(double x) {
+#pragma clang fp contract(off)
   double q, t;
   qr_pow4dd(x, q, t);
   const double p = x * q, e = fma(x, q, -p);

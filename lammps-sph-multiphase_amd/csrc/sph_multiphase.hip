@@ -96,8 +96,12 @@ int sph_hip_atoms_multiphase(sph_hip_ctx *c, const double *rmass, const double *
   SPH_REQUIRE(c && rmass, SPH_HIP_EINVAL, "sph_hip_atoms_multiphase: bad argument");
   SPH_HIP_TRY(hipSetDevice(c->device));
   const size_t nall = (size_t)c->nlocal + c->nghost;
-  c->have_mp_atoms = true;
-  if (nall == 0) return SPH_HIP_OK;
+  // (staged only once the arrays are up: a rejected call leaves nothing a style may read)
+  c->have_mp_atoms = false;
+  if (nall == 0) {
+    c->have_mp_atoms = true;
+    return SPH_HIP_OK;
+  }
   for (size_t i = 0; i < nall; i++)
     SPH_REQUIRE(rmass[i] > 0.0, SPH_HIP_EINVAL, "atom %zu has rmass %g <= 0", i, rmass[i]);
   c->rm.reserve(nall);
@@ -108,6 +112,7 @@ int sph_hip_atoms_multiphase(sph_hip_ctx *c, const double *rmass, const double *
     for (size_t i = 0; i < nall; i++) h[i] = cv[i];
   SPH_HIP_TRY(hipMemcpyAsync(c->cv.p, h.data(), nall * sizeof(double), hipMemcpyHostToDevice, c->stream));
   SPH_HIP_TRY(hipStreamSynchronize(c->stream));
+  c->have_mp_atoms = true;
   SPH_API_END
 }
 
@@ -149,9 +154,10 @@ int sph_hip_taitwater_multiphase_coeff(sph_hip_ctx *c, const double *rho0,
   SPH_API_BEGIN
   SPH_REQUIRE(c && rho0 && soundspeed && gamma && rbackground && viscosity && cut,
               SPH_HIP_EINVAL, "sph_hip_taitwater_multiphase_coeff: NULL argument");
-  for (int t = 1; t <= c->ntypes; t++) {
+  for (int t = 1; t <= c->ntypes; t++)  // (before any table is touched)
     SPH_REQUIRE(gamma[t] != 0.0 && rho0[t] != 0.0, SPH_HIP_EINVAL,
                 "type %d: gamma and rho0 must be non-zero", t);
+  for (int t = 1; t <= c->ntypes; t++) {
     c->hm.rho0[t] = rho0[t];
     c->hm.gamma[t] = gamma[t];
     c->hm.rbg[t] = rbackground[t];
