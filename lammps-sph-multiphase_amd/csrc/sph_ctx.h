@@ -199,14 +199,11 @@ struct sph_hip_ctx {
                          off.p, ilist.p, rown.p);
     int endbit = 1;
     while ((1u << endbit) < (unsigned)(nall + 1) && endbit < 31) endbit++;
-    if (tot) {
-      size_t tb = 0;
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, nbr.p, rkey.p, rown.p, rnbr.p,
-                                                     tot, 0, endbit, stream));
-      tmp.reserve(tb);
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, nbr.p, rkey.p, rown.p, rnbr.p,
-                                                     tot, 0, endbit, stream));
-    }
+    if (tot)
+      with_scratch(tmp, [&](void *t, size_t &tb) {
+        return hipcub::DeviceRadixSort::SortPairs(t, tb, nbr.p, rkey.p, rown.p, rnbr.p, tot, 0,
+                                                  endbit, stream);
+      });
     hipLaunchKernelGGL(k_rev_offsets, dim3((nrows + 1 + 255) / 256), dim3(256), 0, stream,
                        nrows, tot, rkey.p, roff.p);
     SPH_HIP_TRY(hipGetLastError());

@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cstring>
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "sph_coef.h"
@@ -416,7 +417,29 @@ struct sph_engine {
     pending.clear();
   }
 
-  void tmp_reserve(size_t b) { tmp.reserve(b); }
+  // Shorthands on the engine's stream.  launch: a 1-D grid of blocks(n) x BLK threads, no
+  // dynamic LDS (any other geometry or stream spells out hipLaunchKernelGGL); the copies take
+  // element counts; cub: a hipcub device-wide call over the scratch tmp (with_scratch)
+  template <class K, class... A>
+  void launch(K k, long n, A &&...a) {
+    hipLaunchKernelGGL(k, dim3(blocks(n)), dim3(BLK), 0, s, std::forward<A>(a)...);
+  }
+  template <class T>
+  void to_host(T *dst, const T *src, size_t n) {
+    SPH_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
+  }
+  template <class T>
+  void to_dev(T *dst, const T *src, size_t n) {
+    SPH_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+  }
+  template <class T>
+  void dev_copy(T *dst, const T *src, size_t n) {
+    SPH_HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+  }
+  template <class Call>
+  void cub(Call call) {
+    with_scratch(tmp, call);
+  }
 
   void ensure_atoms(size_t nall, bool keep) {
     xf.reserve(nall, keep, s);
@@ -434,10 +457,8 @@ struct sph_engine {
   void mpx_copy(int n, const int *src, int first, DBuf<double> &buf) {
     if (!mp || n <= 0) return;
     buf.reserve((size_t)MPX * n, false, s);
-    hipLaunchKernelGGL(k_mpx_pack, dim3(blocks(n)), dim3(BLK), 0, s, n, src, vel.p, rm.p, cvv.p,
-                       cg.p, buf.p);
-    hipLaunchKernelGGL(k_mpx_unpack, dim3(blocks(n)), dim3(BLK), 0, s, n, (const int *)nullptr,
-                       first, buf.p, vel.p, rm.p, cvv.p, cg.p);
+    launch(k_mpx_pack, n, n, src, vel.p, rm.p, cvv.p, cg.p, buf.p);
+    launch(k_mpx_unpack, n, n, (const int *)nullptr, first, buf.p, vel.p, rm.p, cvv.p, cg.p);
   }
   bool nt1() const { return cfg.ntypes == 1; }
   // the block force pass's viscosity variant: one type with Monaghan viscosity and viscC = 0
@@ -488,9 +509,9 @@ struct sph_engine {
     cs_mx.reserve(2);
     SPH_HIP_TRY(hipMemsetAsync(cs_cnt.p, 0, ((size_t)K + 1) * sizeof(int), s));
     SPH_HIP_TRY(hipMemsetAsync(cs_mx.p + w, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_cs_hist, dim3(blocks(n)), dim3(BLK), 0, s, n, b, xf.p, bkey.p,
-                       (int *)bkey2.p, cs_cnt.p, K, cs_mx.p + w, morton, hdim);
-    SPH_HIP_TRY(hipMemcpyAsync(h_cs + w, cs_mx.p + w, sizeof(int), hipMemcpyDeviceToHost, s));
+    launch(k_cs_hist, n, n, b, xf.p, bkey.p, (int *)bkey2.p, cs_cnt.p, K, cs_mx.p + w, morton,
+           hdim);
+    to_host(h_cs + w, cs_mx.p + w, 1);
     if (prev != 0) {
       SPH_HIP_TRY(hipStreamSynchronize(s));
       cs_prev[w] = h_cs[w];
@@ -499,10 +520,9 @@ struct sph_engine {
       SPH_HIP_TRY(hipEventRecord(cs_ev[w], s));
       cs_pending[w] = true;
     }
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cs_cnt.p, beg, K + 1, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cs_cnt.p, beg, K + 1, s));
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, cs_cnt.p, beg, K + 1, s);
+    });
     return true;
   }
 
@@ -571,31 +591,26 @@ struct sph_engine {
     // key by index, as the stable radix sort's), else the radix sort
     cs_flags &= ~SPH_STAT_CSORT_ROWS;
     if (cs_count(1, n, 1ll << kb, kbn, morton, cfg.dim, cs_beg)) {
-      hipLaunchKernelGGL(k_cs_scatter, dim3(blocks(n)), dim3(BLK), 0, s, n, bkey.p,
-                         (const int *)bkey2.p, cs_beg.p, bidx.p);
-      hipLaunchKernelGGL(k_cs_place<false>, dim3(blocks(n)), dim3(BLK), 0, s, n, bkey.p,
-                         cs_beg.p, bidx.p, bidx2.p, (const double4 *)nullptr,
-                         (const int *)nullptr, (double4 *)nullptr, (int *)nullptr,
-                         (int *)nullptr, 0);
+      launch(k_cs_scatter, n, n, bkey.p, (const int *)bkey2.p, cs_beg.p, bidx.p);
+      launch(k_cs_place<false>, n, n, bkey.p, cs_beg.p, bidx.p, bidx2.p, (const double4 *)nullptr,
+             (const int *)nullptr, (double4 *)nullptr, (int *)nullptr, (int *)nullptr, 0);
       cs_flags |= SPH_STAT_CSORT_ROWS;
     } else {
-      hipLaunchKernelGGL(k_bin_keys, dim3(blocks(n)), dim3(BLK), 0, s, n, 0, kbn, xf.p, bkey.p,
-                         bidx.p, morton, cfg.dim);
-      size_t tb = 0;
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
-      tmp_reserve(tb);
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb, s));
+      launch(k_bin_keys, n, n, 0, kbn, xf.p, bkey.p, bidx.p, morton, cfg.dim);
+      cub([&](void *t, size_t &tb) {
+        return hipcub::DeviceRadixSort::SortPairs(t, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, n, 0, kb,
+                                                  s);
+      });
     }
     // twins of equal capacity: the swaps below then never reallocate (a growing twin would
     // cost a hipMalloc + a synchronising hipFree at every rebuild)
     if (mp) {  // the extra fields in the new order, packed before the permutation
       xbuf.reserve((size_t)MPX * n, false, s);
-      hipLaunchKernelGGL(k_mpx_pack, dim3(blocks(n)), dim3(BLK), 0, s, n, bidx2.p, vel.p, rm.p,
-                         cvv.p, cg.p, xbuf.p);
+      launch(k_mpx_pack, n, n, bidx2.p, vel.p, rm.p, cvv.p, cg.p, xbuf.p);
     }
     grow_twins();
-    hipLaunchKernelGGL(k_permute, dim3(blocks(n)), dim3(BLK), 0, s, n, bidx2.p, xf.p, vr.p,
-                       en.p, ty.p, vel.p, tag.p, xf2.p, vr2.p, en2.p, ty2.p, vel2.p, tag2.p);
+    launch(k_permute, n, n, bidx2.p, xf.p, vr.p, en.p, ty.p, vel.p, tag.p, xf2.p, vr2.p, en2.p,
+           ty2.p, vel2.p, tag2.p);
     std::swap(xf, xf2);
     std::swap(vr, vr2);
     std::swap(en, en2);
@@ -604,13 +619,11 @@ struct sph_engine {
     std::swap(tag, tag2);
     if (pc) {  // (the LAMMPS index rides along)
       lidx2.reserve_exact(lidx.cap);
-      hipLaunchKernelGGL(k_lidx_take, dim3(blocks(n)), dim3(BLK), 0, s, n, bidx2.p, lidx.p, 0,
-                         (const int *)nullptr, lidx2.p);
+      launch(k_lidx_take, n, n, bidx2.p, lidx.p, 0, (const int *)nullptr, lidx2.p);
       std::swap(lidx, lidx2);
     }
     if (mp)
-      hipLaunchKernelGGL(k_mpx_unpack, dim3(blocks(n)), dim3(BLK), 0, s, n, (const int *)nullptr,
-                         0, xbuf.p, vel.p, rm.p, cvv.p, cg.p);
+      launch(k_mpx_unpack, n, n, (const int *)nullptr, 0, xbuf.p, vel.p, rm.p, cvv.p, cg.p);
   }
 
   // the sort's twins at the capacity of the arrays they swap with; called again at the end
@@ -631,23 +644,24 @@ struct sph_engine {
   bool want_blk() const { return cfg.kernel_path == 0; }
 
   int read_scalar(const int *dptr) {
-    SPH_HIP_TRY(hipMemcpyAsync(h_scalar, dptr, sizeof(int), hipMemcpyDeviceToHost, s));
+    to_host(h_scalar, dptr, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     return *h_scalar;
   }
 
   // CommBrick::setup slabs (comm_brick.cpp:330-380) + borders (:696-864) on one process
 
-  // ordered indices i in [0, n) with flag[i] != 0 -> out (returns the count; host sync)
-  int select_flagged(const unsigned char *flag, int n, DBuf<int> &out) {
-    out.reserve(n > 0 ? n : 1);
+  // ordered indices i in [0, n) with flag[i] != 0 (byte or int flags) -> out (returns the
+  // count; host sync)
+  template <class F>
+  int select_flagged(const F *flag, int n, DBuf<int> &out) {
+    out.reserve_min1(n);
     nsel.reserve(1);
     if (n == 0) return 0;
     hipcub::CountingInputIterator<int> it(0);
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flag, out.p, nsel.p, n, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, flag, out.p, nsel.p, n, s));
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceSelect::Flagged(t, tb, it, flag, out.p, nsel.p, n, s);
+    });
     return read_scalar(nsel.p);
   }
 
@@ -656,8 +670,34 @@ struct sph_engine {
     if (remote) {
       tr->exchange(cbs.p, sbytes, dest, cbr.p, rbytes, src, s);
     } else if (rbytes) {
-      SPH_HIP_TRY(hipMemcpyAsync(cbr.p, cbs.p, rbytes, hipMemcpyDeviceToDevice, s));
+      dev_copy(cbr.p, cbs.p, rbytes);
     }
+  }
+
+  // A dimension's two swaps as ONE move of rec-byte records.  Both send from the same atoms
+  // (owned + earlier dimensions' ghosts, see borders_multi) and receive into disjoint ghost
+  // ranges: pack(sw, buf) fills each swap's part of one send buffer (b's part 256-byte
+  // aligned behind a's), one exchange carries both (one RCCL group over xGMI per dimension
+  // instead of one per swap) and unpack(sw, buf) reads each received part.  pack and unpack
+  // are called only for a swap that sends / receives.
+  template <class Pack, class Unpack>
+  void swap_pair(Swap &a, Swap &b, size_t rec, Pack pack, Unpack unpack) {
+    const size_t sa = (size_t)a.nsend * rec, sb = (size_t)b.nsend * rec;
+    const size_t ra = (size_t)a.nrecv * rec, rb = (size_t)b.nrecv * rec;
+    const size_t so = (sa + 255) & ~(size_t)255, ro = (ra + 255) & ~(size_t)255;
+    cbs.reserve(std::max<size_t>(so + sb, 1), true, s);
+    cbr.reserve(std::max<size_t>(ro + rb, 1), true, s);
+    if (a.nsend) pack(a, cbs.p);
+    if (b.nsend) pack(b, cbs.p + so);
+    if (a.remote) {
+      tr->exchange2(cbs.p, sa, a.sendproc, cbr.p, ra, a.recvproc, cbs.p + so, sb, b.sendproc,
+                    cbr.p + ro, rb, b.recvproc, s);
+    } else {  // this brick is its own neighbour along this dimension (periodic self swap)
+      if (ra) dev_copy(cbr.p, cbs.p, ra);
+      if (rb) dev_copy(cbr.p + ro, cbs.p + so, rb);
+    }
+    if (a.nrecv) unpack(a, cbr.p);
+    if (b.nrecv) unpack(b, cbr.p + ro);
   }
 
   // CommBrick::borders over a procgrid (comm_brick.cpp:690-880, maxneed = 1).  Both swaps
@@ -691,7 +731,7 @@ struct sph_engine {
         // the selection's count stays on the device (nsel[dir]); both swaps' counts and the
         // peers' are read back together below: one host sync per dimension
         nsel.reserve(2);
-        sw.list.reserve(nlast > 0 ? nlast : 1);
+        sw.list.reserve_min1(nlast);
         sw.lo_sel = sendflag ? sw.lo : 1.0;  // (no send: an empty slab)
         sw.hi_sel = sendflag ? sw.hi : 0.0;
       }
@@ -719,34 +759,13 @@ struct sph_engine {
         b.nrecv = h[3];
       } else {
         int *const h = h_small;  // (pinned)
-        SPH_HIP_TRY(hipMemcpyAsync(h, nsel.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+        to_host(h, nsel.p, 2);
         SPH_HIP_TRY(hipStreamSynchronize(s));
         a.nsend = a.nrecv = h[0];
         b.nsend = b.nrecv = h[1];
       }
       a.firstrecv = nall;
       b.firstrecv = nall + a.nrecv;
-      const size_t rec = sizeof(BorderRec);
-      const size_t sa = (size_t)a.nsend * rec, sb = (size_t)b.nsend * rec;
-      const size_t ra = (size_t)a.nrecv * rec, rb = (size_t)b.nrecv * rec;
-      const size_t so = (sa + 255) & ~(size_t)255, ro = (ra + 255) & ~(size_t)255;
-      cbs.reserve(std::max<size_t>(so + sb, 1), true, s);
-      cbr.reserve(std::max<size_t>(ro + rb, 1), true, s);
-      for (int dir = 0; dir < 2; dir++) {
-        Swap &sw = *pair[dir];
-        if (sw.nsend)
-          hipLaunchKernelGGL(k_pack_border, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                             sw.list.p, d, sw.shift, sw.pbc, tr->rank(), nlocal, xf.p, vr.p,
-                             en.p, ty.p, gorank.p, goidx.p, gimg.p,
-                             (BorderRec *)(cbs.p + (dir ? so : 0)));
-      }
-      if (a.remote) {
-        tr->exchange2(cbs.p, sa, a.sendproc, cbr.p, ra, a.recvproc, cbs.p + so, sb, b.sendproc,
-                      cbr.p + ro, rb, b.recvproc, s);
-      } else {
-        if (ra) SPH_HIP_TRY(hipMemcpyAsync(cbr.p, cbs.p, ra, hipMemcpyDeviceToDevice, s));
-        if (rb) SPH_HIP_TRY(hipMemcpyAsync(cbr.p + ro, cbs.p + so, rb, hipMemcpyDeviceToDevice, s));
-      }
       const int nr = a.nrecv + b.nrecv;
       if (nr) {
         ensure_atoms((size_t)nall + nr, true);
@@ -755,14 +774,16 @@ struct sph_engine {
         goidx.reserve(ngn, true, s);
         gimg.reserve(ngn, true, s);
       }
-      for (int dir = 0; dir < 2; dir++) {
-        Swap &sw = *pair[dir];
-        if (sw.nrecv)
-          hipLaunchKernelGGL(k_unpack_border, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s,
-                             sw.nrecv, sw.firstrecv, nlocal,
-                             (const BorderRec *)(cbr.p + (dir ? ro : 0)), xf.p, vr.p, en.p,
-                             ty.p, gorank.p, goidx.p, gimg.p);
-      }
+      swap_pair(
+          a, b, sizeof(BorderRec),
+          [&](Swap &sw, unsigned char *buf) {
+            launch(k_pack_border, sw.nsend, sw.nsend, sw.list.p, d, sw.shift, sw.pbc, tr->rank(),
+                   nlocal, xf.p, vr.p, en.p, ty.p, gorank.p, goidx.p, gimg.p, (BorderRec *)buf);
+          },
+          [&](Swap &sw, unsigned char *buf) {
+            launch(k_unpack_border, sw.nrecv, sw.nrecv, sw.firstrecv, nlocal,
+                   (const BorderRec *)buf, xf.p, vr.p, en.p, ty.p, gorank.p, goidx.p, gimg.p);
+          });
       if (mp) mpx_swap_pair(a, b);
       nall += nr;
     }
@@ -786,28 +807,26 @@ struct sph_engine {
     // the ghosts grouped by origin rank on the device (a stable radix sort of (rank, ghost)
     // keeps the ghost order within a rank), the per-rank counts the only read-back
     std::vector<int> beg(P + 2, 0);
-    dr_byq.reserve(ng > 0 ? ng : 1);
-    dr_byg.reserve(ng > 0 ? ng : 1);
+    dr_byq.reserve_min1(ng);
+    dr_byg.reserve_min1(ng);
     dr_hist.reserve(P + 2);
     if (ng) {
       bkey.reserve(ng);
       bkey2.reserve(ng);
       bidx.reserve(ng);
       bidx2.reserve(ng);
-      hipLaunchKernelGGL(k_dr_keys, dim3(blocks(ng)), dim3(BLK), 0, s, ng, P, gorank.p, bkey.p,
-                         bidx.p);
+      launch(k_dr_keys, ng, ng, P, gorank.p, bkey.p, bidx.p);
       int eb = 1;
       while ((1 << eb) <= P) eb++;
-      size_t tb = 0;
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, ng, 0, eb, s));
-      tmp_reserve(tb);
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, ng, 0, eb, s));
-      hipLaunchKernelGGL(k_dr_group, dim3(blocks(ng)), dim3(BLK), 0, s, ng, bidx2.p, goidx.p,
-                         dr_byq.p, dr_byg.p);
+      cub([&](void *t, size_t &tb) {
+        return hipcub::DeviceRadixSort::SortPairs(t, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, ng, 0,
+                                                  eb, s);
+      });
+      launch(k_dr_group, ng, ng, bidx2.p, goidx.p, dr_byq.p, dr_byg.p);
       // beg[r]: the first ghost of rank r (r = 0 .. P + 1; ranks out of range sort as P)
       hipLaunchKernelGGL(k_lower_bound, dim3(1), dim3(64 * ((P + 2 + 63) / 64)), 0, s, P + 1,
                          ng, 0, bkey2.p, dr_hist.p);
-      SPH_HIP_TRY(hipMemcpyAsync(beg.data(), dr_hist.p, (P + 2) * sizeof(int), hipMemcpyDeviceToHost, s));
+      to_host(beg.data(), dr_hist.p, P + 2);
       SPH_HIP_TRY(hipStreamSynchronize(s));
     }
     SPH_REQUIRE(beg[P + 1] == beg[P], SPH_HIP_ERUNTIME,
@@ -832,20 +851,20 @@ struct sph_engine {
     // the peers' groups are the rank-ordered groups without this rank's own (unless the
     // loopback sends those through the communicator): two device copies
     DBuf<int> &req = dr_req;  // (persistent: no hipMalloc / synchronising hipFree per rebuild)
-    req.reserve(R > 0 ? R : 1);
-    dr_sidx.reserve(S > 0 ? S : 1);
-    dr_rslot.reserve(R > 0 ? R : 1);
+    req.reserve_min1(R);
+    dr_sidx.reserve_min1(S);
+    dr_rslot.reserve_min1(R);
     {
       const size_t a = loopback ? (size_t)ng : (size_t)beg[me];
       const size_t b0 = loopback ? (size_t)ng : (size_t)beg[me + 1];
       SPH_REQUIRE(a + (ng - b0) == R, SPH_HIP_ERUNTIME, "direct forward: %zu != %zu", a + (ng - b0), R);
       if (a) {
-        SPH_HIP_TRY(hipMemcpyAsync(req.p, dr_byq.p, a * sizeof(int), hipMemcpyDeviceToDevice, s));
-        SPH_HIP_TRY(hipMemcpyAsync(dr_rslot.p, dr_byg.p, a * sizeof(int), hipMemcpyDeviceToDevice, s));
+        dev_copy(req.p, dr_byq.p, a);
+        dev_copy(dr_rslot.p, dr_byg.p, a);
       }
       if (ng > (int)b0) {
-        SPH_HIP_TRY(hipMemcpyAsync(req.p + a, dr_byq.p + b0, (ng - b0) * sizeof(int), hipMemcpyDeviceToDevice, s));
-        SPH_HIP_TRY(hipMemcpyAsync(dr_rslot.p + a, dr_byg.p + b0, (ng - b0) * sizeof(int), hipMemcpyDeviceToDevice, s));
+        dev_copy(req.p + a, dr_byq.p + b0, ng - b0);
+        dev_copy(dr_rslot.p + a, dr_byg.p + b0, ng - b0);
       }
     }
     dr_sb.resize(np);
@@ -861,9 +880,9 @@ struct sph_engine {
     tr->exchange_multi(np, dr_peer.data(), dr_sb.data(), dr_sbytes.data(), dr_rb.data(),
                        dr_rbytes.data(), s);
     dr_nself = loopback ? 0 : beg[me + 1] - beg[me];
-    dr_self.reserve(dr_nself > 0 ? dr_nself : 1);
+    dr_self.reserve_min1(dr_nself);
     if (dr_nself)
-      SPH_HIP_TRY(hipMemcpyAsync(dr_self.p, dr_byg.p + beg[me], dr_nself * sizeof(int), hipMemcpyDeviceToDevice, s));
+      dev_copy(dr_self.p, dr_byg.p + beg[me], dr_nself);
     dr_ok = true;
   }
   // one direct forward of rec-byte records: pack the send lists, one exchange, unpack
@@ -889,60 +908,22 @@ struct sph_engine {
   // the extra multiphase fields of a dimension's two swaps (pack_border_vel / pack_comm_vel
   // of atom_vec_meso_multiphase.cpp): lists -> the peers -> firstrecv..
   void mpx_swap_pair(Swap &a, Swap &b) {
-    const size_t rec = MPX * sizeof(double);
-    const size_t sa = (size_t)a.nsend * rec, sb = (size_t)b.nsend * rec;
-    const size_t ra = (size_t)a.nrecv * rec, rb = (size_t)b.nrecv * rec;
-    const size_t so = (sa + 255) & ~(size_t)255, ro = (ra + 255) & ~(size_t)255;
-    cbs.reserve(std::max<size_t>(so + sb, 1), true, s);
-    cbr.reserve(std::max<size_t>(ro + rb, 1), true, s);
-    if (a.nsend)
-      hipLaunchKernelGGL(k_mpx_pack, dim3(blocks(a.nsend)), dim3(BLK), 0, s, a.nsend, a.list.p,
-                         vel.p, rm.p, cvv.p, cg.p, (double *)cbs.p);
-    if (b.nsend)
-      hipLaunchKernelGGL(k_mpx_pack, dim3(blocks(b.nsend)), dim3(BLK), 0, s, b.nsend, b.list.p,
-                         vel.p, rm.p, cvv.p, cg.p, (double *)(cbs.p + so));
-    if (a.remote) {
-      tr->exchange2(cbs.p, sa, a.sendproc, cbr.p, ra, a.recvproc, cbs.p + so, sb, b.sendproc,
-                    cbr.p + ro, rb, b.recvproc, s);
-    } else {
-      if (ra) SPH_HIP_TRY(hipMemcpyAsync(cbr.p, cbs.p, ra, hipMemcpyDeviceToDevice, s));
-      if (rb) SPH_HIP_TRY(hipMemcpyAsync(cbr.p + ro, cbs.p + so, rb, hipMemcpyDeviceToDevice, s));
-    }
-    if (a.nrecv)
-      hipLaunchKernelGGL(k_mpx_unpack, dim3(blocks(a.nrecv)), dim3(BLK), 0, s, a.nrecv,
-                         (const int *)nullptr, a.firstrecv, (const double *)cbr.p, vel.p, rm.p,
-                         cvv.p, cg.p);
-    if (b.nrecv)
-      hipLaunchKernelGGL(k_mpx_unpack, dim3(blocks(b.nrecv)), dim3(BLK), 0, s, b.nrecv,
-                         (const int *)nullptr, b.firstrecv, (const double *)(cbr.p + ro), vel.p,
-                         rm.p, cvv.p, cg.p);
+    swap_pair(
+        a, b, MPX * sizeof(double),
+        [&](Swap &sw, unsigned char *buf) {
+          launch(k_mpx_pack, sw.nsend, sw.nsend, sw.list.p, vel.p, rm.p, cvv.p, cg.p,
+                 (double *)buf);
+        },
+        [&](Swap &sw, unsigned char *buf) {
+          launch(k_mpx_unpack, sw.nrecv, sw.nrecv, (const int *)nullptr, sw.firstrecv,
+                 (const double *)buf, vel.p, rm.p, cvv.p, cg.p);
+        });
   }
 
-  // Per-step forward traffic, one dimension at a time: the two swaps of a dimension send
-  // from the same atoms (owned + earlier dimensions' ghosts, see borders_multi) and
-  // receive into disjoint ghost ranges, so both are packed into one buffer and moved as
-  // ONE exchange (one RCCL group over xGMI per dimension instead of one per swap).
+  // Per-step forward traffic, one dimension at a time (swap_pair)
   template <class Pack, class Unpack>
   void forward_dims(size_t rec, Pack pack, Unpack unpack) {
-    for (int k = 0; k + 1 < nswap; k += 2) {
-      Swap &a = swaps[k], &b = swaps[k + 1];
-      const size_t sa = (size_t)a.nsend * rec, sb = (size_t)b.nsend * rec;
-      const size_t ra = (size_t)a.nrecv * rec, rb = (size_t)b.nrecv * rec;
-      const size_t so = (sa + 255) & ~(size_t)255, ro = (ra + 255) & ~(size_t)255;
-      cbs.reserve(std::max<size_t>(so + sb, 1), true, s);
-      cbr.reserve(std::max<size_t>(ro + rb, 1), true, s);
-      if (a.nsend) pack(a, cbs.p);
-      if (b.nsend) pack(b, cbs.p + so);
-      if (a.remote) {
-        tr->exchange2(cbs.p, sa, a.sendproc, cbr.p, ra, a.recvproc, cbs.p + so, sb, b.sendproc,
-                      cbr.p + ro, rb, b.recvproc, s);
-      } else {  // this brick is its own neighbour along this dimension (periodic self swap)
-        if (ra) SPH_HIP_TRY(hipMemcpyAsync(cbr.p, cbs.p, ra, hipMemcpyDeviceToDevice, s));
-        if (rb) SPH_HIP_TRY(hipMemcpyAsync(cbr.p + ro, cbs.p + so, rb, hipMemcpyDeviceToDevice, s));
-      }
-      if (a.nrecv) unpack(a, cbr.p);
-      if (b.nrecv) unpack(b, cbr.p + ro);
-    }
+    for (int k = 0; k + 1 < nswap; k += 2) swap_pair(swaps[k], swaps[k + 1], rec, pack, unpack);
   }
 
   // Comm::forward_comm (x, vest, rho, e)
@@ -951,30 +932,27 @@ struct sph_engine {
       forward_direct(
           9 * sizeof(double),
           [&](int n, unsigned char *buf) {
-            hipLaunchKernelGGL(k_pack_direct, dim3(blocks(n)), dim3(BLK), 0, s, n, dr_sidx.p,
-                               xf.p, vr.p, en.p, (double *)buf);
+            launch(k_pack_direct, n, n, dr_sidx.p, xf.p, vr.p, en.p, (double *)buf);
           },
           [&](int n, unsigned char *buf) {
-            hipLaunchKernelGGL(k_unpack_direct, dim3(blocks(n)), dim3(BLK), 0, s, n,
-                               dr_rslot.p, nlocal, box, gimg.p, (const double *)buf, xf.p, vr.p,
-                               en.p);
+            launch(k_unpack_direct, n, n, dr_rslot.p, nlocal, box, gimg.p, (const double *)buf,
+                   xf.p, vr.p, en.p);
           },
           [&] {
-            hipLaunchKernelGGL(k_forward_self, dim3(blocks(dr_nself)), dim3(BLK), 0, s,
-                               dr_nself, dr_self.p, nlocal, box, goidx.p, gimg.p, xf.p, vr.p,
-                               en.p);
+            launch(k_forward_self, dr_nself, dr_nself, dr_self.p, nlocal, box, goidx.p, gimg.p,
+                   xf.p, vr.p, en.p);
           });
       return;
     }
     forward_dims(
         9 * sizeof(double),
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_pack_forward, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                             sw.list.p, sw.dim, sw.shift, xf.p, vr.p, en.p, (double *)buf);
+          launch(k_pack_forward, sw.nsend, sw.nsend, sw.list.p, sw.dim, sw.shift, xf.p, vr.p, en.p,
+                 (double *)buf);
         },
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_unpack_forward, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s,
-                             sw.nrecv, sw.firstrecv, (const double *)buf, xf.p, vr.p, en.p);
+          launch(k_unpack_forward, sw.nrecv, sw.nrecv, sw.firstrecv, (const double *)buf, xf.p,
+                 vr.p, en.p);
         });
     if (mp)
       for (int k = 0; k + 1 < nswap; k += 2) mpx_swap_pair(swaps[k], swaps[k + 1]);
@@ -984,23 +962,17 @@ struct sph_engine {
   void reverse1(double *a) {
     if (!multi()) {
       if (nghost)
-        hipLaunchKernelGGL(k_reverse1, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost, nlocal,
-                           gowner.p, a);
+        launch(k_reverse1, nghost, nghost, nlocal, gowner.p, a);
       return;
     }
-    for (int k = nswap - 1; k >= 0; k--) {
-      Swap &sw = swaps[k];
-      cbs.reserve((size_t)(sw.nrecv > 0 ? sw.nrecv : 1) * sizeof(double), true, s);
-      cbr.reserve((size_t)(sw.nsend > 0 ? sw.nsend : 1) * sizeof(double), true, s);
-      if (sw.nrecv)
-        hipLaunchKernelGGL(k_pack_rev1, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s, sw.nrecv,
-                           sw.firstrecv, a, (double *)cbs.p);
-      swap_move(sw.remote, (size_t)sw.nrecv * sizeof(double), sw.recvproc,
-                (size_t)sw.nsend * sizeof(double), sw.sendproc);
-      if (sw.nsend)
-        hipLaunchKernelGGL(k_unpack_rev1, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                           sw.list.p, (const double *)cbr.p, a);
-    }
+    reverse_swaps(
+        sizeof(double),
+        [&](Swap &sw) {
+          launch(k_pack_rev1, sw.nrecv, sw.nrecv, sw.firstrecv, a, (double *)cbs.p);
+        },
+        [&](Swap &sw) {
+          launch(k_unpack_rev1, sw.nsend, sw.nsend, sw.list.p, (const double *)cbr.p, a);
+        });
   }
 
   // comm->forward_comm_pair of sph/rhosum: rho (+ the EOS term)
@@ -1009,46 +981,54 @@ struct sph_engine {
       forward_direct(
           sizeof(double2),
           [&](int n, unsigned char *buf) {
-            hipLaunchKernelGGL(k_pack_rho, dim3(blocks(n)), dim3(BLK), 0, s, n, dr_sidx.p, xf.p,
-                               vr.p, (double2 *)buf);
+            launch(k_pack_rho, n, n, dr_sidx.p, xf.p, vr.p, (double2 *)buf);
           },
           [&](int n, unsigned char *buf) {
-            hipLaunchKernelGGL(k_unpack_rho_direct, dim3(blocks(n)), dim3(BLK), 0, s, n,
-                               dr_rslot.p, nlocal, (const double2 *)buf, xf.p, vr.p);
+            launch(k_unpack_rho_direct, n, n, dr_rslot.p, nlocal, (const double2 *)buf, xf.p, vr.p);
           },
           [&] {
-            hipLaunchKernelGGL(k_forward_rho_self, dim3(blocks(dr_nself)), dim3(BLK), 0, s,
-                               dr_nself, dr_self.p, nlocal, goidx.p, xf.p, vr.p);
+            launch(k_forward_rho_self, dr_nself, dr_nself, dr_self.p, nlocal, goidx.p, xf.p, vr.p);
           });
       return;
     }
     forward_dims(
         sizeof(double2),
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_pack_rho, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                             sw.list.p, xf.p, vr.p, (double2 *)buf);
+          launch(k_pack_rho, sw.nsend, sw.nsend, sw.list.p, xf.p, vr.p, (double2 *)buf);
         },
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_unpack_rho, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s, sw.nrecv,
-                             sw.firstrecv, (const double2 *)buf, xf.p, vr.p);
+          launch(k_unpack_rho, sw.nrecv, sw.nrecv, sw.firstrecv, (const double2 *)buf, xf.p, vr.p);
         });
   }
 
-  // Comm::reverse_comm (f, drho, de): swaps in reverse order, ghosts back to senders
-  void reverse_multi() {
+  // The swaps in reverse order, ghosts back to their senders: pack(sw) fills cbs from the
+  // nrecv ghosts of a swap, unpack(sw) adds cbr to the nsend atoms of its list (rec bytes each)
+  template <class Pack, class Unpack>
+  void reverse_swaps(size_t rec, Pack pack, Unpack unpack) {
     for (int k = nswap - 1; k >= 0; k--) {
       Swap &sw = swaps[k];
-      cbs.reserve((size_t)(sw.nrecv > 0 ? sw.nrecv : 1) * 5 * sizeof(double), true, s);
-      cbr.reserve((size_t)(sw.nsend > 0 ? sw.nsend : 1) * 5 * sizeof(double), true, s);
-      if (sw.nrecv)
-        hipLaunchKernelGGL(k_pack_reverse, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s, sw.nrecv,
-                           sw.firstrecv, fo.p, de.p, (double *)cbs.p);
-      swap_move(sw.remote, (size_t)sw.nrecv * 5 * sizeof(double), sw.recvproc,
-                (size_t)sw.nsend * 5 * sizeof(double), sw.sendproc);
-      if (sw.nsend)
-        hipLaunchKernelGGL(k_unpack_reverse, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                           sw.list.p, (const double *)cbr.p, fo.p, de.p);
+      cbs.reserve((size_t)(sw.nrecv > 0 ? sw.nrecv : 1) * rec, true, s);
+      cbr.reserve((size_t)(sw.nsend > 0 ? sw.nsend : 1) * rec, true, s);
+      if (sw.nrecv) pack(sw);
+      swap_move(sw.remote, (size_t)sw.nrecv * rec, sw.recvproc, (size_t)sw.nsend * rec,
+                sw.sendproc);
+      if (sw.nsend) unpack(sw);
     }
+  }
+
+  // Comm::reverse_comm (f, drho, de).  No caller today: the step's full lists are gather-only,
+  // so nothing goes back to the owners; it stays for a half-list (newton) pass on bricks and
+  // is untested until one exists.
+  void reverse_multi() {
+    reverse_swaps(
+        5 * sizeof(double),
+        [&](Swap &sw) {
+          launch(k_pack_reverse, sw.nrecv, sw.nrecv, sw.firstrecv, fo.p, de.p, (double *)cbs.p);
+        },
+        [&](Swap &sw) {
+          launch(k_unpack_reverse, sw.nsend, sw.nsend, sw.list.p, (const double *)cbr.p, fo.p,
+                 de.p);
+        });
   }
 
   // CommBrick::exchange (comm_brick.cpp:573-680): atoms that left the brick along each
@@ -1057,23 +1037,20 @@ struct sph_engine {
     for (int d = 0; d < cfg.dim; d++) {
       if (pg[d] == 1) continue;
       const int n = nlocal;
-      flags.reserve(n > 0 ? n : 1);
-      flag2.reserve(n > 0 ? n : 1);
+      flags.reserve_min1(n);
+      flag2.reserve_min1(n);
       if (n)
-        hipLaunchKernelGGL(k_flag_leave, dim3(blocks(n)), dim3(BLK), 0, s, n, d, sublo[d],
-                           subhi[d], xf.p, flags.p, flag2.p);
+        launch(k_flag_leave, n, n, d, sublo[d], subhi[d], xf.p, flags.p, flag2.p);
       const int nl = select_flagged(flags.p, n, sel);
       migrations += nl;
       const int nst = select_flagged(flag2.p, n, sel2);
       if (pc && nl) hole_fill(n, nl, nst);  // (leavers put in send order, lidx renumbered)
       cbs.reserve((size_t)(nl > 0 ? nl : 1) * sizeof(MigRec));
       if (nl)
-        hipLaunchKernelGGL(k_pack_mig, dim3(blocks(nl)), dim3(BLK), 0, s, nl, sel.p, xf.p,
-                           vr.p, vel.p, en.p, ty.p, tag.p, (MigRec *)cbs.p);
+        launch(k_pack_mig, nl, nl, sel.p, xf.p, vr.p, vel.p, en.p, ty.p, tag.p, (MigRec *)cbs.p);
       if (mp && nl) {  // the leavers' extra fields
         xbuf.reserve((size_t)MPX * nl, false, s);
-        hipLaunchKernelGGL(k_mpx_pack, dim3(blocks(nl)), dim3(BLK), 0, s, nl, sel.p, vel.p,
-                           rm.p, cvv.p, cg.p, xbuf.p);
+        launch(k_mpx_pack, nl, nl, sel.p, vel.p, rm.p, cvv.p, cg.p, xbuf.p);
       }
       if (nl) {  // compact the staying atoms to the front (order kept)
         DBuf<unsigned char> keep;
@@ -1081,13 +1058,12 @@ struct sph_engine {
         // (every record is packed from the old rows before any row is rewritten: the extra
         // fields' copy rewrites vel, which the records carry whole)
         if (nst)
-          hipLaunchKernelGGL(k_pack_mig, dim3(blocks(nst)), dim3(BLK), 0, s, nst, sel2.p, xf.p,
-                             vr.p, vel.p, en.p, ty.p, tag.p, (MigRec *)keep.p);
+          launch(k_pack_mig, nst, nst, sel2.p, xf.p, vr.p, vel.p, en.p, ty.p, tag.p,
+                 (MigRec *)keep.p);
         mpx_copy(nst, sel2.p, 0, xbuf2);
         if (nst)
-          hipLaunchKernelGGL(k_gather_mig, dim3(blocks(nst)), dim3(BLK), 0, s, nst,
-                             (const int *)nullptr, (const MigRec *)keep.p, 0, xf.p, vr.p,
-                             vel.p, en.p, ty.p, tag.p);
+          launch(k_gather_mig, nst, nst, (const int *)nullptr, (const MigRec *)keep.p, 0, xf.p,
+                 vr.p, vel.p, en.p, ty.p, tag.p);
         SPH_HIP_TRY(hipStreamSynchronize(s));
         keep.release();
       }
@@ -1108,28 +1084,26 @@ struct sph_engine {
         }
         if (nr == 0) continue;
         flags.reserve(nr);
-        hipLaunchKernelGGL(k_flag_mine, dim3(blocks(nr)), dim3(BLK), 0, s, nr, d, sublo[d],
-                           subhi[d], (const MigRec *)cbr.p, flags.p);
+        launch(k_flag_mine, nr, nr, d, sublo[d], subhi[d], (const MigRec *)cbr.p, flags.p);
         const int nm = select_flagged(flags.p, nr, sel2);
         if (nm == 0) continue;
         ensure_atoms((size_t)nlocal + nm, true);
         vel.reserve((size_t)nlocal + nm, true, s);
         tag.reserve((size_t)nlocal + nm, true, s);
-        hipLaunchKernelGGL(k_gather_mig, dim3(blocks(nm)), dim3(BLK), 0, s, nm, sel2.p,
-                           (const MigRec *)cbr.p, nlocal, xf.p, vr.p, vel.p, en.p, ty.p, tag.p);
+        launch(k_gather_mig, nm, nm, sel2.p, (const MigRec *)cbr.p, nlocal, xf.p, vr.p, vel.p, en.p,
+               ty.p, tag.p);
         if (pc) {  // unpack_exchange appends in buffer order
           lidx.reserve((size_t)nlocal + nm, true, s);
-          hipLaunchKernelGGL(k_lidx_iota, dim3(blocks(nm)), dim3(BLK), 0, s, nm, nlocal,
-                             lidx.p + nlocal);
+          launch(k_lidx_iota, nm, nm, nlocal, lidx.p + nlocal);
         }
         if (mp)
-          hipLaunchKernelGGL(k_mpx_unpack, dim3(blocks(nm)), dim3(BLK), 0, s, nm, sel2.p,
-                             nlocal, (const double *)xbuf2.p, vel.p, rm.p, cvv.p, cg.p);
+          launch(k_mpx_unpack, nm, nm, sel2.p, nlocal, (const double *)xbuf2.p, vel.p, rm.p, cvv.p,
+                 cg.p);
         nlocal += nm;
       }
     }
-    fo.reserve(nlocal > 0 ? nlocal : 1, true, s);
-    de.reserve(nlocal > 0 ? nlocal : 1, true, s);
+    fo.reserve_min1(nlocal, true, s);
+    de.reserve_min1(nlocal, true, s);
   }
 
   // CommBrick::exchange's scan of one dimension (comm_brick.cpp:620-632) on the LAMMPS
@@ -1141,10 +1115,9 @@ struct sph_engine {
   void hole_fill(int n, int nl, int nst) {
     std::vector<int> hl(nl), hr(nl);
     lidx_tab.reserve(nl);
-    hipLaunchKernelGGL(k_lidx_take, dim3(blocks(nl)), dim3(BLK), 0, s, nl, sel.p, lidx.p, 0,
-                       (const int *)nullptr, lidx_tab.p);
-    SPH_HIP_TRY(hipMemcpyAsync(hl.data(), lidx_tab.p, nl * sizeof(int), hipMemcpyDeviceToHost, s));
-    SPH_HIP_TRY(hipMemcpyAsync(hr.data(), sel.p, nl * sizeof(int), hipMemcpyDeviceToHost, s));
+    launch(k_lidx_take, nl, nl, sel.p, lidx.p, 0, (const int *)nullptr, lidx_tab.p);
+    to_host(hl.data(), lidx_tab.p, nl);
+    to_host(hr.data(), sel.p, nl);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     std::vector<int> ord(nl);
     for (int k = 0; k < nl; k++) ord[k] = k;
@@ -1179,13 +1152,12 @@ struct sph_engine {
                                        [&](int a, int val) { return hl[a] < val; });
       rows[k] = hr[*it];
     }
-    SPH_HIP_TRY(hipMemcpyAsync(sel.p, rows.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
-    SPH_HIP_TRY(hipMemcpyAsync(lidx_tab.p, tab.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
+    to_dev(sel.p, rows.data(), nl);
+    to_dev(lidx_tab.p, tab.data(), nl);
     if (nst) {
       lidx2.reserve_exact(lidx.cap);
-      hipLaunchKernelGGL(k_lidx_take, dim3(blocks(nst)), dim3(BLK), 0, s, nst, sel2.p, lidx.p,
-                         nst, lidx_tab.p, lidx2.p);
-      SPH_HIP_TRY(hipMemcpyAsync(lidx.p, lidx2.p, nst * sizeof(int), hipMemcpyDeviceToDevice, s));
+      launch(k_lidx_take, nst, nst, sel2.p, lidx.p, nst, lidx_tab.p, lidx2.p);
+      dev_copy(lidx.p, lidx2.p, nst);
     }
     SPH_HIP_TRY(hipStreamSynchronize(s));  // (host vectors)
   }
@@ -1216,38 +1188,32 @@ struct sph_engine {
     skey2.reserve(n);
     srow.reserve(n);
     srow2.reserve(n);
-    hipLaunchKernelGGL(k_lidx_sortkeys, dim3(blocks(n)), dim3(BLK), 0, s, n, b, xf.p, lidx.p,
-                       skey.p, srow.p);
+    launch(k_lidx_sortkeys, n, n, b, xf.p, lidx.p, skey.p, srow.p);
     int hb = 32;
     while ((double)(1ll << (hb - 32)) < nbins) hb++;
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, skey.p, skey2.p, srow.p, srow2.p,
-                                                   n, 0, hb, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, skey.p, skey2.p, srow.p, srow2.p,
-                                                   n, 0, hb, s));
-    hipLaunchKernelGGL(k_lidx_rank, dim3(blocks(n)), dim3(BLK), 0, s, n, srow2.p, lidx.p);
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, skey.p, skey2.p, srow.p, srow2.p, n, 0, hb,
+                                                s);
+    });
+    launch(k_lidx_rank, n, n, srow2.p, lidx.p);
   }
 
   // the LAMMPS indices from the tags: read order (tag order) -- set_atoms, read_restart
   void lidx_from_tags() {
     const int n = nlocal;
-    lidx.reserve(n > 0 ? n : 1);
+    lidx.reserve_min1(n);
     lidx_valid = true;
     if (n == 0) return;
     skey.reserve(n);
     skey2.reserve(n);
     srow.reserve(n);
     srow2.reserve(n);
-    hipLaunchKernelGGL(k_lidx_tagkeys, dim3(blocks(n)), dim3(BLK), 0, s, n, tag.p, skey.p,
-                       srow.p);
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, skey.p, skey2.p, srow.p, srow2.p,
-                                                   n, 0, 32, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, skey.p, skey2.p, srow.p, srow2.p,
-                                                   n, 0, 32, s));
-    hipLaunchKernelGGL(k_lidx_rank, dim3(blocks(n)), dim3(BLK), 0, s, n, srow2.p, lidx.p);
+    launch(k_lidx_tagkeys, n, n, tag.p, skey.p, srow.p);
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, skey.p, skey2.p, srow.p, srow2.p, n, 0, 32,
+                                                s);
+    });
+    launch(k_lidx_rank, n, n, srow2.p, lidx.p);
   }
 
   // One brick: CommBrick::borders' self swaps (comm_brick.cpp:696-864) with every count kept
@@ -1282,9 +1248,8 @@ struct sph_engine {
       if (pc) gsrc.reserve(gcap, true, s);
       h_small[14] = nlocal;  // (pinned; the read-back below lands in words 0 .. nsw + 1)
       h_small[15] = 0;       // the overflow word
-      SPH_HIP_TRY(hipMemcpyAsync(gnall.p, h_small + 14, sizeof(int), hipMemcpyHostToDevice, s));
-      SPH_HIP_TRY(hipMemcpyAsync(gnall.p + nsw + 1, h_small + 15, sizeof(int),
-                                 hipMemcpyHostToDevice, s));
+      to_dev(gnall.p, h_small + 14, 1);
+      to_dev(gnall.p + nsw + 1, h_small + 15, 1);
       int w = 0;
       // a dimension's two swaps in three launches (k_brd_count / scan / scatter)
       for (int d = 0; d < ndim; d++) {
@@ -1304,8 +1269,7 @@ struct sph_engine {
                            mp ? cvv.p : (double *)nullptr, mp ? cg.p : (double4 *)nullptr);
         w += 2;
       }
-      SPH_HIP_TRY(hipMemcpyAsync(h_small, gnall.p, (nsw + 2) * sizeof(int),
-                                 hipMemcpyDeviceToHost, s));
+      to_host(h_small, gnall.p, nsw + 2);
       SPH_HIP_TRY(hipStreamSynchronize(s));
       if (h_small[nsw + 1] == 0) break;
       SPH_REQUIRE(gcap < 1000000000, SPH_HIP_EOVERFLOW, "ghost count exceeds 2^30");
@@ -1325,23 +1289,24 @@ struct sph_engine {
   // the same ghosts in our own (Hilbert) order; sort each swap by that key: grank[g] = the
   // ghost's LAMMPS slot.  Used only when a created atom may overwrite a slot a candidate reads.
   void pc_ghost_slots() {
-    pc_grank.reserve(nghost > 0 ? nghost : 1);
+    pc_grank.reserve_min1(nghost);
     for (size_t w = 0; w + 1 < gswap_first.size(); w++) {
       const int first = gswap_first[w], ns = gswap_first[w + 1] - first;
       if (ns == 0) continue;
       pc_key.reserve(2 * (size_t)ns);
       pc_val.reserve(2 * (size_t)ns);
-      hipLaunchKernelGGL(k_pc_swapkeys, dim3(blocks(ns)), dim3(BLK), 0, s, ns, first, gsrc.p,
-                         nlocal, lidx.p, pc_grank.p, pc_key.p, pc_val.p);
-      size_t tb = 0;
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, pc_key.p, pc_key.p + ns,
-                                                     pc_val.p, pc_val.p + ns, ns, 0, 32, s));
-      tmp_reserve(tb);
-      SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, pc_key.p, pc_key.p + ns,
-                                                     pc_val.p, pc_val.p + ns, ns, 0, 32, s));
-      hipLaunchKernelGGL(k_pc_swaprank, dim3(blocks(ns)), dim3(BLK), 0, s, ns, first,
-                         pc_val.p + ns, pc_grank.p);
+      launch(k_pc_swapkeys, ns, ns, first, gsrc.p, nlocal, lidx.p, pc_grank.p, pc_key.p, pc_val.p);
+      pc_rank_swap(ns, first, 32);
     }
+  }
+  // a swap's ns ghosts from slot `first` on: pc_key / pc_val sorted by the low `bits` key bits
+  // (into their upper halves), the ghosts' ranks from that order
+  void pc_rank_swap(int ns, int first, int bits) {
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, pc_key.p, pc_key.p + ns, pc_val.p,
+                                                pc_val.p + ns, ns, 0, bits, s);
+    });
+    launch(k_pc_swaprank, ns, ns, first, pc_val.p + ns, pc_grank.p);
   }
 
   // Bricks: the same slot order, but a swap's ghosts come from another rank, whose scan
@@ -1349,45 +1314,21 @@ struct sph_engine {
   // dimension's two swaps send that key along the send lists (one exchange), the receiver
   // sorts each swap by it.  Collective over the ranks (every rank calls it).
   void pc_ghost_slots_multi() {
-    pc_grank.reserve(nghost > 0 ? nghost : 1);
-    for (int k = 0; k + 1 < nswap; k += 2) {
-      Swap &a = swaps[k], &b = swaps[k + 1];
-      const size_t sa = (size_t)a.nsend * 4, sb = (size_t)b.nsend * 4;
-      const size_t ra = (size_t)a.nrecv * 4, rb = (size_t)b.nrecv * 4;
-      const size_t so = (sa + 255) & ~(size_t)255, ro = (ra + 255) & ~(size_t)255;
-      cbs.reserve(std::max<size_t>(so + sb, 1), true, s);
-      cbr.reserve(std::max<size_t>(ro + rb, 1), true, s);
-      if (a.nsend)
-        hipLaunchKernelGGL(k_pc_sendkeys, dim3(blocks(a.nsend)), dim3(BLK), 0, s, a.nsend,
-                           a.list.p, nlocal, lidx.p, pc_grank.p, (int *)cbs.p);
-      if (b.nsend)
-        hipLaunchKernelGGL(k_pc_sendkeys, dim3(blocks(b.nsend)), dim3(BLK), 0, s, b.nsend,
-                           b.list.p, nlocal, lidx.p, pc_grank.p, (int *)(cbs.p + so));
-      if (a.remote) {
-        tr->exchange2(cbs.p, sa, a.sendproc, cbr.p, ra, a.recvproc, cbs.p + so, sb, b.sendproc,
-                      cbr.p + ro, rb, b.recvproc, s);
-      } else {
-        if (ra) SPH_HIP_TRY(hipMemcpyAsync(cbr.p, cbs.p, ra, hipMemcpyDeviceToDevice, s));
-        if (rb) SPH_HIP_TRY(hipMemcpyAsync(cbr.p + ro, cbs.p + so, rb, hipMemcpyDeviceToDevice, s));
-      }
-      for (int dir = 0; dir < 2; dir++) {
-        Swap &sw = dir ? b : a;
-        const int ns = sw.nrecv, first = sw.firstrecv - nlocal;
-        if (ns == 0) continue;
-        pc_key.reserve(2 * (size_t)ns);
-        pc_val.reserve(2 * (size_t)ns);
-        hipLaunchKernelGGL(k_pc_keys_in, dim3(blocks(ns)), dim3(BLK), 0, s, ns,
-                           (const int *)(cbr.p + (dir ? ro : 0)), pc_key.p, pc_val.p);
-        size_t tb = 0;
-        SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, pc_key.p, pc_key.p + ns,
-                                                       pc_val.p, pc_val.p + ns, ns, 0, 31, s));
-        tmp_reserve(tb);
-        SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, pc_key.p, pc_key.p + ns,
-                                                       pc_val.p, pc_val.p + ns, ns, 0, 31, s));
-        hipLaunchKernelGGL(k_pc_swaprank, dim3(blocks(ns)), dim3(BLK), 0, s, ns, first,
-                           pc_val.p + ns, pc_grank.p);
-      }
-    }
+    pc_grank.reserve_min1(nghost);
+    for (int k = 0; k + 1 < nswap; k += 2)
+      swap_pair(
+          swaps[k], swaps[k + 1], sizeof(int),
+          [&](Swap &sw, unsigned char *buf) {
+            launch(k_pc_sendkeys, sw.nsend, sw.nsend, sw.list.p, nlocal, lidx.p, pc_grank.p,
+                   (int *)buf);
+          },
+          [&](Swap &sw, unsigned char *buf) {
+            const int ns = sw.nrecv;
+            pc_key.reserve(2 * (size_t)ns);
+            pc_val.reserve(2 * (size_t)ns);
+            launch(k_pc_keys_in, ns, ns, (const int *)buf, pc_key.p, pc_val.p);
+            pc_rank_swap(ns, sw.firstrecv - nlocal, 31);
+          });
   }
 
   // The neighbour and ghost cutoffs from cutmax_tab, the checks that depend on them, and the
@@ -1486,36 +1427,29 @@ struct sph_engine {
     // the two apart); else the radix sort, k_lower_bound and k_bin_copy
     cs_flags &= ~SPH_STAT_CSORT_BINS;
     if (cs_count(0, nall, nqbins, b, 0, 3, qbeg)) {
-      hipLaunchKernelGGL(k_cs_scatter, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
-                         (const int *)bkey2.p, qbeg.p, bidx.p);
+      launch(k_cs_scatter, nall, nall, bkey.p, (const int *)bkey2.p, qbeg.p, bidx.p);
       if (csort == 2) {
-        hipLaunchKernelGGL(k_cs_place<false>, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
-                           qbeg.p, bidx.p, bidx2.p, (const double4 *)nullptr,
-                           (const int *)nullptr, (double4 *)nullptr, (int *)nullptr,
-                           (int *)nullptr, 0);
-        hipLaunchKernelGGL(k_bin_copy, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bidx2.p, xf.p,
-                           ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
+        launch(k_cs_place<false>, nall, nall, bkey.p, qbeg.p, bidx.p, bidx2.p,
+               (const double4 *)nullptr, (const int *)nullptr, (double4 *)nullptr, (int *)nullptr,
+               (int *)nullptr, 0);
+        launch(k_bin_copy, nall, nall, bidx2.p, xf.p, ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
       } else {
-        hipLaunchKernelGGL(k_cs_place<true>, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bkey.p,
-                           qbeg.p, bidx.p, (int *)nullptr, xf.p, ty.p, xb.p, tb.p, xpos.p,
-                           mp ? 1 : 0);
+        launch(k_cs_place<true>, nall, nall, bkey.p, qbeg.p, bidx.p, (int *)nullptr, xf.p, ty.p,
+               xb.p, tb.p, xpos.p, mp ? 1 : 0);
       }
       cs_flags |= SPH_STAT_CSORT_BINS;
       return;
     }
-    hipLaunchKernelGGL(k_bin_keys, dim3(blocks(nall)), dim3(BLK), 0, s, nall, 0, b, xf.p,
-                       bkey.p, bidx.p, 0);
+    launch(k_bin_keys, nall, nall, 0, b, xf.p, bkey.p, bidx.p, 0, 3);  // (linear keys: hdim unused)
     int endbit = 1;
     while ((1u << endbit) < (unsigned)nqbins && endbit < 32) endbit++;
-    size_t tbytes = 0;
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tbytes, bkey.p, bkey2.p, bidx.p, bidx2.p, nall, 0, endbit, s));
-    tmp_reserve(tbytes);
-    SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tbytes, bkey.p, bkey2.p, bidx.p, bidx2.p, nall, 0, endbit, s));
-    hipLaunchKernelGGL(k_lower_bound, dim3(blocks(nqbins + 1)), dim3(BLK), 0, s, nqbins, nall,
-                       0, bkey2.p, qbeg.p);
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, nall, 0,
+                                                endbit, s);
+    });
+    launch(k_lower_bound, nqbins + 1, nqbins, nall, 0, bkey2.p, qbeg.p);
     xpos.reserve(nall);
-    hipLaunchKernelGGL(k_bin_copy, dim3(blocks(nall)), dim3(BLK), 0, s, nall, bidx2.p, xf.p,
-                       ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
+    launch(k_bin_copy, nall, nall, bidx2.p, xf.p, ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
   }
   // Global-index full list (k_neigh3, Neighbor::full_bin membership) of the owned rows at
   // positions xi (default: the current ones, as binned by bin_q): CSR (count pass, scan,
@@ -1535,7 +1469,7 @@ struct sph_engine {
     off.reserve(n + 1);
     constexpr int G = 8;
     dim3 grid(grid_for_rows(n, G)), block(BLK);
-    auto launch = [&](bool fill, int stride, int *dst = nullptr) {
+    auto pass = [&](bool fill, int stride, int *dst = nullptr) {
       if (n == 0) return;
       const bool t = nt1();
       // asymmetric multiphase styles (k_mp_gather): owned pairs take the half-list orientation
@@ -1584,7 +1518,7 @@ struct sph_engine {
       list_tbits = !nt1() && tbits_env() && !mp;
       nbr.reserve((size_t)n * list_stride);
       SPH_HIP_TRY(hipMemsetAsync(mx.p, 0, sizeof(int), s));
-      launch(true, list_stride);
+      pass(true, list_stride);
       if (read_scalar(mx.p) == 0) {
         strided = true;
         nbr_total = -1;  // entries counted on demand (stats)
@@ -1603,33 +1537,32 @@ struct sph_engine {
       list_perm_g = 0;
       nbs.reserve((size_t)n * list_stride);
       SPH_HIP_TRY(hipMemsetAsync(mx.p, 0, sizeof(int), s));
-      launch(true, list_stride, nbs.p);
+      pass(true, list_stride, nbs.p);
       filled = read_scalar(mx.p) == 0;
     }
-    if (!filled) launch(false, 0);
-    hipLaunchKernelGGL(k_copy_counts, dim3(blocks(n + 1)), dim3(BLK), 0, s, n, ccnt.p, off.p);
-    size_t tb2 = 0;
-    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, off.p, off.p, n + 1, s));
-    tmp_reserve(tb2);
-    SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb2, off.p, off.p, n + 1, s));
-    size_t tb3 = 0;
-    SPH_HIP_TRY(hipcub::DeviceReduce::Max(nullptr, tb3, ccnt.p, mx.p + 1, n, s));
-    tmp_reserve(tb3);
-    if (n > 0) SPH_HIP_TRY(hipcub::DeviceReduce::Max(tmp.p, tb3, ccnt.p, mx.p + 1, n, s));
+    if (!filled) pass(false, 0);
+    launch(k_copy_counts, n + 1, n, ccnt.p, off.p);
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceScan::ExclusiveSum(t, tb, off.p, off.p, n + 1, s);
+    });
+    if (n > 0)
+      cub([&](void *t, size_t &tb) {
+        return hipcub::DeviceReduce::Max(t, tb, ccnt.p, mx.p + 1, n, s);
+      });
     else SPH_HIP_TRY(hipMemsetAsync(mx.p + 1, 0, sizeof(int), s));
     int hm[2];
-    SPH_HIP_TRY(hipMemcpyAsync(&hm[0], off.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
-    SPH_HIP_TRY(hipMemcpyAsync(&hm[1], mx.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    to_host(&hm[0], off.p + n, 1);
+    to_host(&hm[1], mx.p + 1, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     const int tot = hm[0];
     SPH_REQUIRE(tot >= 0, SPH_HIP_EOVERFLOW, "neighbor list exceeds 2^31 entries");
-    nbr.reserve(tot > 0 ? tot : 1);
+    nbr.reserve_min1(tot);
     if (filled) {
       if (n)
         hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)(((long)n * 32 + BLK - 1) / BLK)),
                            dim3(BLK), 0, s, n, list_stride, ccnt.p, off.p, nbs.p, nbr.p);
     } else {
-      launch(true, 0);
+      pass(true, 0);
     }
     // stride of later single-pass builds: this build's longest row + 25% + 16, 64-aligned
     // (whole chunks of the transposed layout, 16-B aligned rows)
@@ -1703,7 +1636,7 @@ struct sph_engine {
       inner_written = v2 && want_inner;
       // the build's statistics: ONE read-back
       int *const hm = h_small;
-      SPH_HIP_TRY(hipMemcpyAsync(hm, mx.p, 9 * sizeof(int), hipMemcpyDeviceToHost, s));
+      to_host(hm, mx.p, 9);
       SPH_HIP_TRY(hipStreamSynchronize(s));
       if (env_int("SPH_DEBUG", 0))
         fprintf(stderr,
@@ -1748,8 +1681,7 @@ struct sph_engine {
         blk_umf = choose_umf(hm[7], (double)hm[8] / nb);
       else
         blk_umf = choose_umf(blk_um, (double)hm[4] / nb);
-      hipLaunchKernelGGL(k_blk_count_big, dim3(blocks(nb)), dim3(BLK), 0, s, nb,
-                         iu ? uicnt.p : ucnt.p, blk_umf, mx.p + 9);
+      launch(k_blk_count_big, nb, nb, iu ? uicnt.p : ucnt.p, blk_umf, mx.p + 9);
       if (env_int("SPH_DEBUG", 0))
         fprintf(stderr, "[sph] inner union max %d mean %.1f; force image %d records\n", hm[7],
                 (double)hm[8] / nb, blk_umf);
@@ -1819,7 +1751,7 @@ struct sph_engine {
   void build_all(bool need_csr) {
     // (the multiphase passes walk global-index full rows carrying each pair's half-list
     // orientation, k_neigh3: CSR at setup, fixed-stride rows once the setup sized them)
-    hipLaunchKernelGGL(k_pbc, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, box, xf.p, vel.p);
+    launch(k_pbc, nlocal, nlocal, box, xf.p, vel.p);
     if (multi()) exchange_multi();
     // Atom::sort between the exchange and borders (verlet.cpp:106, 251): only the LAMMPS
     // indices move -- the rows keep the engine's own order
@@ -1872,7 +1804,7 @@ struct sph_engine {
     x0.reserve(nx0);
     if (!inner_written)  // (k_blk_inner writes the inner unions too)
       blk_inner(nt1(), s, blk_args(), xf.p, ty.p, dc, snbi.p, icnt.p);
-    SPH_HIP_TRY(hipMemcpyAsync(x0.p, xf.p, nx0 * sizeof(double4), hipMemcpyDeviceToDevice, s));
+    dev_copy(x0.p, xf.p, nx0);
     SPH_HIP_TRY(hipMemsetAsync(moved.p, 0, 2 * sizeof(int), s));
     sc.x0 = x0.p;
     sc.lim2 = 0.25 * inner_margin * inner_margin;
@@ -1899,8 +1831,7 @@ struct sph_engine {
     rf.x0 = x0.p;
     blk_inner(nt1(), s, k, xf.p, ty.p, dc, snbi.p, icnt.p, rf);
     if (multi() && nghost)
-      hipLaunchKernelGGL(k_x0_cond, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost, cur,
-                         xf.p + nlocal, x0.p + nlocal);
+      launch(k_x0_cond, nghost, nghost, cur, xf.p + nlocal, x0.p + nlocal);
     inner_refreshes++;
   }
 
@@ -1921,8 +1852,8 @@ struct sph_engine {
     }
     if (blk) {
       const int nb = blk_blocks(n, blk_shape(blk_sh).R);
-      fl_in.reserve(nb > 0 ? nb : 1);
-      fl_bd.reserve(nb > 0 ? nb : 1);
+      fl_in.reserve_min1(nb);
+      fl_bd.reserve_min1(nb);
       if (nb)
         hipLaunchKernelGGL(k_blk_interior, dim3(nb), dim3(64), 0, s, nb, ulist.p, ucnt.p,
                            BLK_UCAP, nlocal, fl_in.p, fl_bd.p);
@@ -1932,8 +1863,8 @@ struct sph_engine {
       ov_ready = true;
       return;
     }
-    fl_in.reserve(n > 0 ? n : 1);
-    fl_bd.reserve(n > 0 ? n : 1);
+    fl_in.reserve_min1(n);
+    fl_bd.reserve_min1(n);
     if (n)
       hipLaunchKernelGGL(k_row_ghost_flags, dim3((unsigned)(((long)n * 8 + 255) / 256)),
                          dim3(256), 0, s, n, nlocal, strided ? nullptr : off.p,
@@ -1975,8 +1906,7 @@ struct sph_engine {
         // (the ghosts' displacement check of forward(): the interior blocks read no ghost,
         // so whether they saw the flag before or after it is harmless)
         if (inner && sc.x0 && nghost)
-          hipLaunchKernelGGL(k_inner_ghosts, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost,
-                             nlocal, sc, xf.p);
+          launch(k_inner_ghosts, nghost, nghost, nlocal, sc, xf.p);
         blk_rhosum(nt1(), s, kb, xf.p, ty.p, vr.p, dc);
         join();
       }
@@ -2030,18 +1960,17 @@ struct sph_engine {
     last_build = (int)step;
     nm_builds++;
     if (!nm_check) return;
-    xhold.reserve(nlocal > 0 ? nlocal : 1);
+    xhold.reserve_min1(nlocal);
     nm_flag.reserve(1);
     if (nlocal)
-      SPH_HIP_TRY(hipMemcpyAsync(xhold.p, xf.p, (size_t)nlocal * sizeof(double4),
-                                 hipMemcpyDeviceToDevice, s));
+      dev_copy(xhold.p, xf.p, (size_t)nlocal);
     SPH_HIP_TRY(hipMemsetAsync(nm_flag.p, 0, sizeof(int), s));
   }
   // The check's answer: this brick's flag (one small copy into pinned memory, one stream
   // synchronise), over bricks the largest (MPI_Allreduce MAX, neighbor.cpp:1407) -- every
   // rank reaches the same eligible steps, a rank without atoms takes part with 0.
   bool neigh_flag_any() {
-    SPH_HIP_TRY(hipMemcpyAsync(h_nm, nm_flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    to_host(h_nm, nm_flag.p, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     int flag = nlocal > 0 ? *h_nm : 0;
     if (multi() && tr) {
@@ -2060,7 +1989,7 @@ struct sph_engine {
     r.dtf = sc.dtf;
     r.brick_min = DT_BIG;
     *h_dt = r;
-    SPH_HIP_TRY(hipMemcpyAsync(dt_rec.p, h_dt, sizeof(DtRecord), hipMemcpyHostToDevice, s));
+    to_dev(dt_rec.p, h_dt, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));  // (h_dt is read back into later)
   }
   // FixDtReset::end_of_step (fix_dt_reset.cpp:131-186) of the current step: the scan over the
@@ -2074,7 +2003,7 @@ struct sph_engine {
   void dt_end_of_step(bool with_final) {
     Scope t(this, T_INT);
     const unsigned nb = blocks(nlocal);
-    dt_part.reserve(nb > 0 ? nb : 1);
+    dt_part.reserve_min1(nb);
     const double *m = rm.p;
     if (nb) {
       if (with_final)
@@ -2091,7 +2020,7 @@ struct sph_engine {
     }
     hipLaunchKernelGGL(k_dt_fold<true>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
                        (long long)step, dt_rec.p);
-    SPH_HIP_TRY(hipMemcpyAsync(h_dt, dt_rec.p, sizeof(DtRecord), hipMemcpyDeviceToHost, s));
+    to_host(h_dt, dt_rec.p, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     uint64_t bits;
     std::memcpy(&bits, &h_dt->brick_min, sizeof bits);
@@ -2113,14 +2042,12 @@ struct sph_engine {
       Scope t(this, T_COMM);
       forward_multi();
       if (inner && sc.x0 && nghost)
-        hipLaunchKernelGGL(k_inner_ghosts, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost,
-                           nlocal, sc, xf.p);
+        launch(k_inner_ghosts, nghost, nghost, nlocal, sc, xf.p);
       return;
     }
     if (nghost == 0) return;
     Scope t(this, T_COMM);
-    hipLaunchKernelGGL(k_forward, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost, nlocal, box,
-                       gowner.p, gimg.p, xf.p, vr.p, en.p);
+    launch(k_forward, nghost, nghost, nlocal, box, gowner.p, gimg.p, xf.p, vr.p, en.p);
     mpx_copy(nghost, gowner.p, nlocal, xbuf);
   }
 
@@ -2148,12 +2075,11 @@ struct sph_engine {
     if (!strided) return nbr_total;
     if (nlocal == 0) return 0;
     blen.reserve(1);
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, tb, ccnt.p, blen.p, nlocal, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceReduce::Sum(tmp.p, tb, ccnt.p, blen.p, nlocal, s));
+    cub([&](void *t, size_t &tb) {
+      return hipcub::DeviceReduce::Sum(t, tb, ccnt.p, blen.p, nlocal, s);
+    });
     long long v = 0;
-    SPH_HIP_TRY(hipMemcpyAsync(&v, blen.p, sizeof(long long), hipMemcpyDeviceToHost, s));
+    to_host(&v, blen.p, 1);
     SPH_HIP_TRY(hipStreamSynchronize(s));
     return v;
   }
@@ -2200,18 +2126,16 @@ struct sph_engine {
         forward_rho_multi();
       } else if (nghost) {
         Scope t(this, T_COMM);
-        hipLaunchKernelGGL(k_forward_rho, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost,
-                           nlocal, gowner.p, xf.p, vr.p);
+        launch(k_forward_rho, nghost, nghost, nlocal, gowner.p, xf.p, vr.p);
       }
     } else if (force_mode & M_TAIT) {
-      hipLaunchKernelGGL(k_eos, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vr.p, ty.p, dc);
+      launch(k_eos, nall, nall, xf.p, vr.p, ty.p, dc);
     }
     // sph/idealgas: 0.4 e/m/rho of owned atoms and ghosts from the current e and rho (the
     // ghosts' came with the halos), before EVERY gas pass -- e moves every step, whether or
     // not rhosum was due
     if ((force_mode & M_GAS) && nall)
-      hipLaunchKernelGGL(k_eos_gas, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vr.p, en.p,
-                         ty.p, dc);
+      launch(k_eos_gas, nall, nall, xf.p, vr.p, en.p, ty.p, dc);
     if (force_mode && setup) {
       setup_forces_full();
     } else if (force_mode && blk) {
@@ -2259,10 +2183,9 @@ struct sph_engine {
   void setup_forces_full() {
     const int n = nlocal, nall = nlocal + nghost;
     if (force_mode == 0 || n == 0) return;
-    vsg.reserve(nghost > 0 ? nghost : 1);
+    vsg.reserve_min1(nghost);
     if (nghost)
-      SPH_HIP_TRY(hipMemcpyAsync(vsg.p, vr.p + n, (size_t)nghost * sizeof(double4),
-                                 hipMemcpyDeviceToDevice, s));
+      dev_copy(vsg.p, vr.p + n, (size_t)nghost);
     forward();  // the ghosts' vest as setup_pre_force left their owners' (x, rho, e unchanged)
     fo.reserve(nall, true, s);
     de.reserve(nall, true, s);
@@ -2296,8 +2219,8 @@ struct sph_engine {
   // reverse comm, without atomics or comm)
   void pair_compute_mp() {
     const int n = nlocal, nall = nlocal + nghost;
-    fo.reserve(n > 0 ? n : 1, true, s);
-    de.reserve(n > 0 ? n : 1, true, s);
+    fo.reserve_min1(n, true, s);
+    de.reserve_min1(n, true, s);
     if (n == 0) return;
     MpArgs a{};
     a.stride = strided ? list_stride : 0;  // (else CSR: off)
@@ -2320,8 +2243,7 @@ struct sph_engine {
     // the stale version: rho and colorgradient as communicated (k_mp_gather)
     rhoS.reserve(nall);
     cgS.reserve(nall);
-    hipLaunchKernelGGL(k_mp_snap, dim3(blocks(nall)), dim3(BLK), 0, s, nall, vr.p, cg.p, rhoS.p,
-                       cgS.p);
+    launch(k_mp_snap, nall, nall, vr.p, cg.p, rhoS.p, cgS.p);
     const bool rdue = mpc.rhosum_nstep > 0 && step % mpc.rhosum_nstep == 0;
     const bool cdue = mpc.cg_nstep > 0 && step % mpc.cg_nstep == 0;
     {
@@ -2333,13 +2255,12 @@ struct sph_engine {
           hipLaunchKernelGGL(k_mp2_rhosum<8>, mp_rows(n), dim3(256), 0, s, a);
         mp_flags = (mp_flags & ~SPH_STAT_MP_RHO_LISTFILL) |
                    (rho_fused_step == step ? SPH_STAT_MP_RHO_LISTFILL : 0);
-        hipLaunchKernelGGL(k_mp_rho_store, dim3(blocks(n)), dim3(BLK), 0, s, n, rho_tmp.p, vr.p);
+        launch(k_mp_rho_store, n, n, rho_tmp.p, vr.p);
       }
       if (cdue) {
         a.cg = cg.p;
         recA.reserve(nall);  // (free until the force pass packs its records)
-        hipLaunchKernelGGL(k_mp_pack_sigma, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vr.p,
-                           rm.p, recA.p);
+        launch(k_mp_pack_sigma, nall, nall, xf.p, vr.p, rm.p, recA.p);
         a.xs = recA.p;
         hipLaunchKernelGGL(k_mp2_colorgradient<8>, mp_rows(n), dim3(256), 0, s, a);
         a.xs = nullptr;
@@ -2352,8 +2273,7 @@ struct sph_engine {
       Scope t(this, T_COMM);
       rhoF.reserve(nall);
       cgF.reserve(nall);
-      hipLaunchKernelGGL(k_mp_snap, dim3(blocks(n)), dim3(BLK), 0, s, n, vr.p, cg.p, rhoF.p,
-                         cgF.p);
+      launch(k_mp_snap, n, n, vr.p, cg.p, rhoF.p, cgF.p);
       forward_fresh();
       rF = rhoF.p;
       cF = cgF.p;
@@ -2377,13 +2297,11 @@ struct sph_engine {
     // symmetric styles (mp2_symmetric): the issue-rate gather of sph_mp2_kernels.h
     const bool sym = mp2_symmetric(hm);
     if (sym)
-      hipLaunchKernelGGL(k_mp2_pack_rec, dim3(blocks(nall)), dim3(BLK), 0, s, nall, cfg.dim,
-                         xf.p, vel.p, rm.p, en.p, cvv.p, rF, rhoS.p, cF, cgS.p,
-                         mpc.heat_on ? 1 : 0, recA.p, recK.p, recF.p, recS.p);
+      launch(k_mp2_pack_rec, nall, nall, cfg.dim, xf.p, vel.p, rm.p, en.p, cvv.p, rF, rhoS.p, cF,
+             cgS.p, mpc.heat_on ? 1 : 0, recA.p, recK.p, recF.p, recS.p);
     else
-      hipLaunchKernelGGL(k_mp_pack_rec, dim3(blocks(nall)), dim3(BLK), 0, s, nall, xf.p, vel.p,
-                         rm.p, en.p, cvv.p, rF, rhoS.p, cF, cgS.p, mpc.heat_on ? 1 : 0, recA.p,
-                         recK.p, recF.p, recS.p);
+      launch(k_mp_pack_rec, nall, nall, xf.p, vel.p, rm.p, en.p, cvv.p, rF, rhoS.p, cF, cgS.p,
+             mpc.heat_on ? 1 : 0, recA.p, recK.p, recF.p, recS.p);
     h.pA = recA.p;
     h.pK = recK.p;
     h.pF = recF.p;
@@ -2418,33 +2336,18 @@ struct sph_engine {
   void forward_fresh() {
     if (!multi()) {
       if (nghost)
-        hipLaunchKernelGGL(k_mp_fwd_fresh, dim3(blocks(nghost)), dim3(BLK), 0, s, nghost, nlocal,
-                           gowner.p, rhoF.p, cgF.p);
+        launch(k_mp_fwd_fresh, nghost, nghost, nlocal, gowner.p, rhoF.p, cgF.p);
       return;
     }
     forward_dims(
         4 * sizeof(double),
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_mp_pack_fresh, dim3(blocks(sw.nsend)), dim3(BLK), 0, s, sw.nsend,
-                             sw.list.p, rhoF.p, cgF.p, (double *)buf);
+          launch(k_mp_pack_fresh, sw.nsend, sw.nsend, sw.list.p, rhoF.p, cgF.p, (double *)buf);
         },
         [&](Swap &sw, unsigned char *buf) {
-          hipLaunchKernelGGL(k_mp_unpack_fresh, dim3(blocks(sw.nrecv)), dim3(BLK), 0, s,
-                             sw.nrecv, sw.firstrecv, (const double *)buf, rhoF.p, cgF.p);
+          launch(k_mp_unpack_fresh, sw.nrecv, sw.nrecv, sw.firstrecv, (const double *)buf, rhoF.p,
+                 cgF.p);
         });
-  }
-
-  // ordered indices i in [0, n) with flag[i] != 0 (int flags) -> out; host sync
-  int select_flagged_i(const int *flag, int n, DBuf<int> &out) {
-    out.reserve(n > 0 ? n : 1);
-    nsel.reserve(1);
-    if (n == 0) return 0;
-    hipcub::CountingInputIterator<int> it(0);
-    size_t tb = 0;
-    SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flag, out.p, nsel.p, n, s));
-    tmp_reserve(tb);
-    SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, flag, out.p, nsel.p, n, s));
-    return read_scalar(nsel.p);
   }
 
   // FixPhaseChange::pre_exchange (fix_phase_change.cpp:167-352) on the last build's full
@@ -2480,9 +2383,8 @@ struct sph_engine {
     int ncand = 0;
     if (n > 0) {
       flag.reserve(n);
-      hipLaunchKernelGGL(k_pc_flags, dim3(blocks(n)), dim3(BLK), 0, s, n, (const int *)nullptr,
-                         ty.p, en.p, cvv.p, pd, flag.p);
-      ncand = select_flagged_i(flag.p, n, cand);
+      launch(k_pc_flags, n, n, (const int *)nullptr, ty.p, en.p, cvv.p, pd, flag.p);
+      ncand = select_flagged(flag.p, n, cand);
     }
     if (ncand == 0 && !mul) return;  // (dmass 0: the finish loop leaves rmass and e as they are)
     const int lst = strided ? list_stride : 0;
@@ -2508,7 +2410,7 @@ struct sph_engine {
       pc_minr.reserve(ncand);
       walk(rk);
       if (!mul) {
-        SPH_HIP_TRY(hipMemcpyAsync(hm.data(), pc_minr.p, ncand * sizeof(int), hipMemcpyDeviceToHost, s));
+        to_host(hm.data(), pc_minr.p, ncand);
         SPH_HIP_TRY(hipStreamSynchronize(s));
         if (std::any_of(hm.begin(), hm.end(), [](int v) { return v != PC_NORANK; })) {
           pc_ghost_slots();
@@ -2516,13 +2418,13 @@ struct sph_engine {
           walk(rk);
         }
       }
-      hipLaunchKernelGGL(k_pc_gather, dim3(blocks(ncand)), dim3(BLK), 0, s, ncand, cand.p, xf.p,
-                         vr.p, en.p, cvv.p, cg.p, lidx.p, gat.p, otag.p);
-      SPH_HIP_TRY(hipMemcpyAsync(hm.data(), pc_minr.p, ncand * sizeof(int), hipMemcpyDeviceToHost, s));
-      SPH_HIP_TRY(hipMemcpyAsync(hc.data(), cand.p, ncand * sizeof(int), hipMemcpyDeviceToHost, s));
-      SPH_HIP_TRY(hipMemcpyAsync(ht.data(), otag.p, ncand * sizeof(int), hipMemcpyDeviceToHost, s));
-      SPH_HIP_TRY(hipMemcpyAsync(hr.data(), rec.p, hr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      SPH_HIP_TRY(hipMemcpyAsync(hg.data(), gat.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      launch(k_pc_gather, ncand, ncand, cand.p, xf.p, vr.p, en.p, cvv.p, cg.p, lidx.p, gat.p,
+             otag.p);
+      to_host(hm.data(), pc_minr.p, ncand);
+      to_host(hc.data(), cand.p, ncand);
+      to_host(ht.data(), otag.p, ncand);
+      to_host(hr.data(), rec.p, hr.size());
+      to_host(hg.data(), gat.p, hg.size());
       SPH_HIP_TRY(hipStreamSynchronize(s));
     }
     mark("readback");
@@ -2548,11 +2450,11 @@ struct sph_engine {
     }
     auto recompute = [&](size_t q, int dead_a, int dead_w, double *out) {
       pc_one.reserve(1);
-      SPH_HIP_TRY(hipMemcpyAsync(pc_one.p, &hc[ord[q]], sizeof(int), hipMemcpyHostToDevice, s));
+      to_dev(pc_one.p, &hc[ord[q]], 1);
       hipLaunchKernelGGL(k_pc_candidates<8>, dim3(1), dim3(256), 0, s, 1, pc_one.p,
                          (const int *)nullptr, off.p, nbr.p, xf.p, vr.p, (const double *)vel.p,
                          4, ty.p, rm.p, pd, Wd.p, lst, ccnt.p, rk, dead_a, dead_w, (int *)nullptr);
-      SPH_HIP_TRY(hipMemcpyAsync(out, Wd.p, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+      to_host(out, Wd.p, 8);
       SPH_HIP_TRY(hipStreamSynchronize(s));
     };
     Wd.reserve(8);
@@ -2589,7 +2491,7 @@ struct sph_engine {
       hval[q] = ins_rec[(size_t)13 * q + 9];
       hW[q] = ins_W[q];
     }
-    dmass.reserve(nall > 0 ? nall : 1);
+    dmass.reserve_min1(nall);
     mark("host");
     if (nall) SPH_HIP_TRY(hipMemsetAsync(dmass.p, 0, nall * sizeof(double), s));
     if (nins) {
@@ -2597,12 +2499,12 @@ struct sph_engine {
       vals.reserve(nins);
       Wd.reserve(nins);
       nrec.reserve((size_t)13 * nins);
-      SPH_HIP_TRY(hipMemcpyAsync(idx.p, hidx.data(), nins * sizeof(int), hipMemcpyHostToDevice, s));
-      SPH_HIP_TRY(hipMemcpyAsync(vals.p, hval.data(), nins * sizeof(double), hipMemcpyHostToDevice, s));
-      SPH_HIP_TRY(hipMemcpyAsync(Wd.p, hW.data(), nins * sizeof(double), hipMemcpyHostToDevice, s));
-      SPH_HIP_TRY(hipMemcpyAsync(nrec.p, ins_rec.data(), ins_rec.size() * sizeof(double), hipMemcpyHostToDevice, s));
+      to_dev(idx.p, hidx.data(), nins);
+      to_dev(vals.p, hval.data(), nins);
+      to_dev(Wd.p, hW.data(), nins);
+      to_dev(nrec.p, ins_rec.data(), ins_rec.size());
       // e_i = (e_i - Hwv)/2 of the atoms that changed phase, the donors' dmass
-      hipLaunchKernelGGL(k_pc_set_e, dim3(blocks(nins)), dim3(BLK), 0, s, nins, idx.p, vals.p, en.p);
+      launch(k_pc_set_e, nins, nins, idx.p, vals.p, en.p);
       // (in candidate order per donor: the reference's sum, fix_phase_change.cpp:289-299)
       const long long cap = (long long)nins * std::max(lst > 0 ? lst : nbr_maxrow, 1);
       pc_dmass_ordered<8>(s, nins, idx.p, Wd.p, (const int *)nullptr, off.p, nbr.p, xf.p, ty.p,
@@ -2612,18 +2514,17 @@ struct sph_engine {
     // its reverse comm, rmass -= dmass and e renormalised, then the new atoms
     reverse1(dmass.p);
     if (n)
-      hipLaunchKernelGGL(k_pc_finish, dim3(blocks(n)), dim3(BLK), 0, s, n, dmass.p, rm.p, en.p);
+      launch(k_pc_finish, n, n, dmass.p, rm.p, en.p);
     if (nins) {
       ensure_atoms((size_t)n + nins, true);  // (over the ghost slots: the rebuild follows)
       vel.reserve((size_t)n + nins, true, s);
       tag.reserve((size_t)n + nins, true, s);
       fo.reserve((size_t)n + nins, true, s);
       de.reserve((size_t)n + nins, true, s);
-      hipLaunchKernelGGL(k_pc_append, dim3(blocks(nins)), dim3(BLK), 0, s, nins, nrec.p, n,
-                         p.to_type, tag0, xf.p, vr.p, vel.p, en.p, rm.p, cvv.p, cg.p, ty.p,
-                         tag.p, fo.p, de.p);
+      launch(k_pc_append, nins, nins, nrec.p, n, p.to_type, tag0, xf.p, vr.p, vel.p, en.p, rm.p,
+             cvv.p, cg.p, ty.p, tag.p, fo.p, de.p);
       lidx.reserve((size_t)n + nins, true, s);  // (create_atom: at the end, in creation order)
-      hipLaunchKernelGGL(k_lidx_iota, dim3(blocks(nins)), dim3(BLK), 0, s, nins, n, lidx.p + n);
+      launch(k_lidx_iota, nins, nins, n, lidx.p + n);
     }
     SPH_HIP_TRY(hipStreamSynchronize(s));  // (the host staging vectors go out of scope)
     mark("end");
@@ -2660,9 +2561,9 @@ struct sph_engine {
     if (sm.nfix == 0 || nlocal == 0) return;
     Scope t(this, T_INT);
     const double cvc = (!mp && sm_needs_cv) ? uniform_cv("fix setmeso meso_t") : 1.0;
-    hipLaunchKernelGGL(k_setmeso, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, sm, xf.p, vr.p,
-                       en.p, de.p, ty.p, mp ? (const double *)cvv.p : nullptr, cvc,
-                       (!mp && (force_mode & M_TAIT)) ? (const Coefs *)dc : nullptr);
+    launch(k_setmeso, nlocal, nlocal, sm, xf.p, vr.p, en.p, de.p, ty.p,
+           mp ? (const double *)cvv.p : nullptr, cvc,
+           (!mp && (force_mode & M_TAIT)) ? (const Coefs *)dc : nullptr);
   }
 
   // the types' masses as configured (sc.mass is the body-force mass: 0 outside gravity_mask)
@@ -2699,8 +2600,7 @@ struct sph_engine {
       hipLaunchKernelGGL(k_forcefix_final, dim3(1), dim3(64), 0, s, nb, a, ff_part.p, ff_tot.p);
     }
     if (nlocal)
-      hipLaunchKernelGGL(k_forcefix, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, a, xf.p, ty.p,
-                         m, tm, fo.p);
+      launch(k_forcefix, nlocal, nlocal, a, xf.p, ty.p, m, tm, fo.p);
   }
 
   bool rhosum_due() const {
@@ -2718,12 +2618,10 @@ struct sph_engine {
     // borders() runs before setup_pre_force: ghosts carry vest as it was (reference order);
     // the setup force pass needs the global-index list for its half-list walk
     build_all(true);
-    vso.reserve(nlocal > 0 ? nlocal : 1);  // (vest before setup_pre_force: setup_forces_full)
+    vso.reserve_min1(nlocal);  // (vest before setup_pre_force: setup_forces_full)
     if (nlocal)
-      SPH_HIP_TRY(hipMemcpyAsync(vso.p, vr.p, (size_t)nlocal * sizeof(double4),
-                                 hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_vest_from_v, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal,
-                       cfg.stationary_mask, ty.p, vel.p, vr.p);
+      dev_copy(vso.p, vr.p, (size_t)nlocal);
+    launch(k_vest_from_v, nlocal, nlocal, cfg.stationary_mask, ty.p, vel.p, vr.p);
     pair_compute(rhosum_due(), /*setup=*/true);
     post_force_setmeso();  // (FixSetMeso::setup calls post_force)
     if (ff_tally) {
@@ -2787,21 +2685,17 @@ struct sph_engine {
         if (chk) {
           const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
           if (k == 0)
-            hipLaunchKernelGGL((k_initial_integrate<true, false>), dim3(blocks(nlocal)), dim3(BLK),
-                               0, s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                               StepOpt<true, false>{nh});
+            launch((k_initial_integrate<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+                   vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
           else
-            hipLaunchKernelGGL((k_final_initial<true, false>), dim3(blocks(nlocal)), dim3(BLK), 0,
-                               s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                               StepOpt<true, false>{nh});
+            launch((k_final_initial<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+                   vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
         } else if (k == 0) {
-          hipLaunchKernelGGL((k_initial_integrate<false, false>), dim3(blocks(nlocal)), dim3(BLK),
-                             0, s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                             StepOpt<false, false>{});
+          launch((k_initial_integrate<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+                 vel.p, fo.p, de.p, rm.p, StepOpt<false, false>{});
         } else {
-          hipLaunchKernelGGL((k_final_initial<false, false>), dim3(blocks(nlocal)), dim3(BLK), 0,
-                             s, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                             StepOpt<false, false>{});
+          launch((k_final_initial<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p,
+                 fo.p, de.p, rm.p, StepOpt<false, false>{});
         }
       }
       bool build = pc_due;
@@ -2847,12 +2741,10 @@ struct sph_engine {
     if (nsteps > 0 && !final_done) {
       Scope t(this, T_INT);
       if (dtr_on)
-        hipLaunchKernelGGL(k_final_integrate_dt, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal,
-                           sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
-                           DtFrom<true>{&dt_rec.p->dtv});
+        launch(k_final_integrate_dt, nlocal, nlocal, sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+               DtFrom<true>{&dt_rec.p->dtv});
       else
-        hipLaunchKernelGGL(k_final_integrate, dim3(blocks(nlocal)), dim3(BLK), 0, s, nlocal, sc,
-                           vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
+        launch(k_final_integrate, nlocal, nlocal, sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
     }
     SPH_HIP_TRY(hipGetLastError());
   }
@@ -3121,10 +3013,10 @@ int sph_engine_set_atoms(sph_engine *e, int n, const double *x, const double *v,
   if (cv)
     for (int i = 0; i < n; i++) e->cv_by_tag[i] = cv[i];
   e->ensure_atoms(n > 0 ? n : 1, false);
-  e->vel.reserve(n > 0 ? n : 1);
-  e->fo.reserve(n > 0 ? n : 1);
-  e->de.reserve(n > 0 ? n : 1);
-  e->tag.reserve(n > 0 ? n : 1);
+  e->vel.reserve_min1(n);
+  e->fo.reserve_min1(n);
+  e->de.reserve_min1(n);
+  e->tag.reserve_min1(n);
   std::vector<double4> hx(n), hv(n), hvel(n);
   std::vector<double> he(n);
   std::vector<int> ht(n), hty(n);
@@ -3137,19 +3029,19 @@ int sph_engine_set_atoms(sph_engine *e, int n, const double *x, const double *v,
     hty[i] = type[i];
   }
   if (n > 0) {
-    SPH_HIP_TRY(hipMemcpyAsync(e->xf.p, hx.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->vr.p, hv.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->vel.p, hvel.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->en.p, he.data(), n * sizeof(double), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->ty.p, hty.data(), n * sizeof(int), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->tag.p, ht.data(), n * sizeof(int), hipMemcpyHostToDevice, e->s));
+    e->to_dev(e->xf.p, hx.data(), n);
+    e->to_dev(e->vr.p, hv.data(), n);
+    e->to_dev(e->vel.p, hvel.data(), n);
+    e->to_dev(e->en.p, he.data(), n);
+    e->to_dev(e->ty.p, hty.data(), n);
+    e->to_dev(e->tag.p, ht.data(), n);
     SPH_HIP_TRY(hipMemsetAsync(e->fo.p, 0, n * sizeof(double4), e->s));
     SPH_HIP_TRY(hipMemsetAsync(e->de.p, 0, n * sizeof(double), e->s));
   }
   // LAMMPS' local order starts as the read order (data-file lines / create_atoms), which is
   // the order handed here -- not necessarily tag order (sph_engine_set_tags may permute)
-  e->lidx.reserve(n > 0 ? n : 1);
-  if (n > 0) hipLaunchKernelGGL(k_lidx_iota, dim3(blocks(n)), dim3(BLK), 0, e->s, n, 0, e->lidx.p);
+  e->lidx.reserve_min1(n);
+  if (n > 0) e->launch(k_lidx_iota, n, n, 0, e->lidx.p);
   e->lidx_valid = true;
   if (e->mp && n > 0) {  // per-type mass, cv (default 1, create_atom), colorgradient 0
     std::vector<double> hm(n), hc(n);
@@ -3157,8 +3049,8 @@ int sph_engine_set_atoms(sph_engine *e, int n, const double *x, const double *v,
       hm[i] = e->cfg.mass[type[i]];
       hc[i] = cv ? cv[i] : 1.0;
     }
-    SPH_HIP_TRY(hipMemcpyAsync(e->rm.p, hm.data(), n * sizeof(double), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->cvv.p, hc.data(), n * sizeof(double), hipMemcpyHostToDevice, e->s));
+    e->to_dev(e->rm.p, hm.data(), n);
+    e->to_dev(e->cvv.p, hc.data(), n);
     SPH_HIP_TRY(hipMemsetAsync(e->cg.p, 0, n * sizeof(double4), e->s));
   }
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
@@ -3183,9 +3075,9 @@ int sph_engine_set_atoms_multiphase(sph_engine *e, const double *rmass, const do
     if (cv) hc[i] = cv[i];
     if (cg) hg[i] = make_double4(cg[3 * i], cg[3 * i + 1], cg[3 * i + 2], 0.0);
   }
-  SPH_HIP_TRY(hipMemcpyAsync(e->rm.p, rmass, n * sizeof(double), hipMemcpyHostToDevice, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(e->cvv.p, hc.data(), n * sizeof(double), hipMemcpyHostToDevice, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(e->cg.p, hg.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
+  e->to_dev(e->rm.p, rmass, n);
+  e->to_dev(e->cvv.p, hc.data(), n);
+  e->to_dev(e->cg.p, hg.data(), n);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   e->setup_done = false;
   SPH_API_END
@@ -3282,8 +3174,7 @@ int sph_engine_reduce(sph_engine *e, int nsel, const sph_reduce_sel *sel, sph_re
   hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(64), 0, e->s, nb, nsel, e->red_part.p,
                      e->red_out.p);
   SPH_HIP_TRY(hipGetLastError());
-  SPH_HIP_TRY(hipMemcpyAsync(out, e->red_out.p, nsel * sizeof(sph_reduce_out),
-                             hipMemcpyDeviceToHost, e->s));
+  e->to_host(out, e->red_out.p, nsel);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   SPH_API_END
 }
@@ -3364,8 +3255,7 @@ int sph_engine_forcefix_total(sph_engine *e, int id, double out[3]) {
   SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL,
               "sph_engine_forcefix_total: call sph_engine_setup first");
   SPH_HIP_TRY(hipSetDevice(e->device));
-  SPH_HIP_TRY(hipMemcpyAsync(out, e->ff_tot.p + 3 * id, 3 * sizeof(double),
-                             hipMemcpyDeviceToHost, e->s));
+  e->to_host(out, e->ff_tot.p + 3 * id, 3);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   SPH_API_END
 }
@@ -3407,16 +3297,13 @@ int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, doub
   e->pf_idx2.reserve(n);
   e->pf_cnt.reserve(nl);
   e->pf_sum.reserve((size_t)std::max(p->nq, 1) * nl);
-  hipLaunchKernelGGL(k_profile_keys, dim3(blocks(n)), dim3(BLK), 0, s, n, a, e->xf.p, e->ty.p,
-                     e->pf_key.p, e->pf_idx.p);
+  e->launch(k_profile_keys, n, n, a, e->xf.p, e->ty.p, e->pf_key.p, e->pf_idx.p);
   int eb = 1;  // (keys 0 .. nlayers; the radix sort is stable, so rows stay in order)
   while (eb < 32 && (1u << eb) <= (unsigned)nl) eb++;
-  size_t tb = 0;
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, e->pf_key.p, e->pf_key2.p,
-                                                 e->pf_idx.p, e->pf_idx2.p, n, 0, eb, s));
-  e->tmp_reserve(tb);
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(e->tmp.p, tb, e->pf_key.p, e->pf_key2.p,
-                                                 e->pf_idx.p, e->pf_idx2.p, n, 0, eb, s));
+  e->cub([&](void *t, size_t &tb) {
+    return hipcub::DeviceRadixSort::SortPairs(t, tb, e->pf_key.p, e->pf_key2.p, e->pf_idx.p,
+                                              e->pf_idx2.p, n, 0, eb, s);
+  });
   hipLaunchKernelGGL(k_profile_fold, dim3(nl), dim3(RED_THREADS), 0, s, n, a, e->pf_key2.p,
                      e->pf_idx2.p, e->vr.p, e->en.p, e->de.p, e->ty.p, e->vel.p,
                      e->mp ? (const double *)e->rm.p : nullptr,
@@ -3426,8 +3313,7 @@ int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, doub
   static_assert(sizeof(long long) == sizeof(int64_t), "count copy");
   SPH_HIP_TRY(hipMemcpyAsync(count, e->pf_cnt.p, nl * sizeof(int64_t), hipMemcpyDeviceToHost, s));
   if (p->nq)
-    SPH_HIP_TRY(hipMemcpyAsync(sum, e->pf_sum.p, (size_t)p->nq * nl * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
+    e->to_host(sum, e->pf_sum.p, (size_t)p->nq * nl);
   SPH_HIP_TRY(hipStreamSynchronize(s));
   SPH_API_END
 }
@@ -3444,13 +3330,13 @@ int sph_engine_get_atoms_multiphase(sph_engine *e, double *rmass, double *cv, do
   std::vector<double4> hg(n, make_double4(0, 0, 0, 0)), hv(n);
   std::vector<int> ht(n), hty(n);
   if (e->mp) {
-    SPH_HIP_TRY(hipMemcpyAsync(hm.data(), e->rm.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(hc.data(), e->cvv.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(hg.data(), e->cg.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
+    e->to_host(hm.data(), e->rm.p, n);
+    e->to_host(hc.data(), e->cvv.p, n);
+    e->to_host(hg.data(), e->cg.p, n);
   }
-  SPH_HIP_TRY(hipMemcpyAsync(hv.data(), e->vr.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hty.data(), e->ty.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(ht.data(), e->tag.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
+  e->to_host(hv.data(), e->vr.p, n);
+  e->to_host(hty.data(), e->ty.p, n);
+  e->to_host(ht.data(), e->tag.p, n);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   const bool local_order = e->multi() || e->global_tags;
   for (int i = 0; i < n; i++) {
@@ -3502,16 +3388,16 @@ int sph_engine_write_restart(sph_engine *e, double *buf, int64_t cap, int *rec_s
   std::vector<double4> hx(n), hv(n), hr(n), hg(n, make_double4(0, 0, 0, 0));
   std::vector<double> he(n), hm(n, 0.0), hc(n, 1.0);
   std::vector<int> ht(n), hty(n);
-  SPH_HIP_TRY(hipMemcpyAsync(hx.data(), e->xf.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hv.data(), e->vel.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hr.data(), e->vr.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(he.data(), e->en.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hty.data(), e->ty.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(ht.data(), e->tag.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
+  e->to_host(hx.data(), e->xf.p, n);
+  e->to_host(hv.data(), e->vel.p, n);
+  e->to_host(hr.data(), e->vr.p, n);
+  e->to_host(he.data(), e->en.p, n);
+  e->to_host(hty.data(), e->ty.p, n);
+  e->to_host(ht.data(), e->tag.p, n);
   if (e->mp) {
-    SPH_HIP_TRY(hipMemcpyAsync(hm.data(), e->rm.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(hc.data(), e->cvv.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(hg.data(), e->cg.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
+    e->to_host(hm.data(), e->rm.p, n);
+    e->to_host(hc.data(), e->cvv.p, n);
+    e->to_host(hg.data(), e->cg.p, n);
   }
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   for (int i = 0; i < n; i++) {
@@ -3611,8 +3497,8 @@ int sph_engine_read_restart(sph_engine *e, int n, const double *buf) {
       hr[i] = make_double4(vest[3 * i], vest[3 * i + 1], vest[3 * i + 2], rho[i]);
       hv[i] = make_double4(v[3 * i], v[3 * i + 1], v[3 * i + 2], (double)img[i]);
     }
-    SPH_HIP_TRY(hipMemcpyAsync(e->vr.p, hr.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
-    SPH_HIP_TRY(hipMemcpyAsync(e->vel.p, hv.data(), n * sizeof(double4), hipMemcpyHostToDevice, e->s));
+    e->to_dev(e->vr.p, hr.data(), n);
+    e->to_dev(e->vel.p, hv.data(), n);
     SPH_HIP_TRY(hipStreamSynchronize(e->s));
   }
   SPH_API_END
@@ -3715,8 +3601,7 @@ int sph_engine_dt_stats(sph_engine *e, sph_dt_stats *out) {
     out->laststep = out->changes = 0;
   } else {
     SPH_HIP_TRY(hipSetDevice(e->device));
-    SPH_HIP_TRY(hipMemcpyAsync(e->h_dt, e->dt_rec.p, sizeof(DtRecord), hipMemcpyDeviceToHost,
-                               e->s));
+    e->to_host(e->h_dt, e->dt_rec.p, 1);
     SPH_HIP_TRY(hipStreamSynchronize(e->s));
     const DtRecord &r = *e->h_dt;
     out->dt = r.dt;
@@ -3763,13 +3648,13 @@ int sph_engine_get_atoms(sph_engine *e, double *x, double *v, double *rho, doubl
   std::vector<double4> hx(n), hv(n), hvel(n), hf(n);
   std::vector<double> hen(n), hde(n);
   std::vector<int> ht(n);
-  SPH_HIP_TRY(hipMemcpyAsync(hx.data(), e->xf.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hv.data(), e->vr.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hvel.data(), e->vel.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hf.data(), e->fo.p, n * sizeof(double4), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hen.data(), e->en.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(hde.data(), e->de.p, n * sizeof(double), hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(ht.data(), e->tag.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
+  e->to_host(hx.data(), e->xf.p, n);
+  e->to_host(hv.data(), e->vr.p, n);
+  e->to_host(hvel.data(), e->vel.p, n);
+  e->to_host(hf.data(), e->fo.p, n);
+  e->to_host(hen.data(), e->en.p, n);
+  e->to_host(hde.data(), e->de.p, n);
+  e->to_host(ht.data(), e->tag.p, n);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   // one brick of a decomposition (or caller tags): local slot order, tag[] names the atom;
   // otherwise the set_atoms order
@@ -3808,9 +3693,8 @@ int sph_engine_neighbor_counts(sph_engine *e, int *numneigh) {
   const int n = e->nlocal;
   if (n == 0) return SPH_HIP_OK;
   std::vector<int> hc(n), ht(n);
-  SPH_HIP_TRY(hipMemcpyAsync(hc.data(), e->ccnt.p, n * sizeof(int),
-                             hipMemcpyDeviceToHost, e->s));
-  SPH_HIP_TRY(hipMemcpyAsync(ht.data(), e->tag.p, n * sizeof(int), hipMemcpyDeviceToHost, e->s));
+  e->to_host(hc.data(), e->ccnt.p, n);
+  e->to_host(ht.data(), e->tag.p, n);
   SPH_HIP_TRY(hipStreamSynchronize(e->s));
   const bool local_order = e->multi() || e->global_tags;
   for (int i = 0; i < n; i++) numneigh[local_order ? i : ht[i]] = hc[i];
@@ -3842,15 +3726,14 @@ int sph_engine_stats_get(sph_engine *e, sph_engine_stats *st) {
   st->n_neigh = e->nlaunch[T_NEIGH];
   st->blk_nbig = 0;
   if (e->blk && e->mx.p) {  // (k_blk_count_big of the last block build)
-    SPH_HIP_TRY(hipMemcpyAsync(&st->blk_nbig, e->mx.p + 9, sizeof(int), hipMemcpyDeviceToHost,
-                               e->s));
+    e->to_host(&st->blk_nbig, e->mx.p + 9, 1);
     SPH_HIP_TRY(hipStreamSynchronize(e->s));
   }
   st->inner_rows = e->inner ? 1 : 0;
   st->inner_live = 0;
   if (e->inner && e->moved.p) {
     int mv = 1;
-    SPH_HIP_TRY(hipMemcpyAsync(&mv, e->moved_flag(), sizeof(int), hipMemcpyDeviceToHost, e->s));
+    e->to_host(&mv, e->moved_flag(), 1);
     SPH_HIP_TRY(hipStreamSynchronize(e->s));
     st->inner_live = mv == 0 ? 1 : 0;
   }

@@ -111,10 +111,9 @@ long long scan_counts(sph_hip_ctx *c, const int *cnt, int n, DBuf<int> &off) {
   off.reserve(n + 1);
   hipLaunchKernelGGL(k_copy_counts, dim3((n + 1 + 255) / 256), dim3(256), 0, c->stream, n, cnt,
                      off.p);
-  size_t tb = 0;
-  SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, off.p, off.p, n + 1, c->stream));
-  c->tmp.reserve(tb);
-  SPH_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(c->tmp.p, tb, off.p, off.p, n + 1, c->stream));
+  with_scratch(c->tmp, [&](void *tmp, size_t &tb) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, tb, off.p, off.p, n + 1, c->stream);
+  });
   int tot = 0;
   SPH_HIP_TRY(hipMemcpyAsync(&tot, off.p + n, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   SPH_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -269,12 +268,10 @@ int sph_hip_build_list(sph_hip_ctx *c, int kind, int64_t key, const double *cutn
                      c->xf.p, c->bkey.p, c->bidx.p, 0, 3);
   int endbit = 1;
   while ((1u << endbit) < (unsigned)nqbins && endbit < 32) endbit++;
-  size_t tb = 0;
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, c->bkey.p, c->bkey2.p, c->bidx.p,
-                                                 c->bidx2.p, nall, 0, endbit, c->stream));
-  c->tmp.reserve(tb);
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(c->tmp.p, tb, c->bkey.p, c->bkey2.p, c->bidx.p,
-                                                 c->bidx2.p, nall, 0, endbit, c->stream));
+  with_scratch(c->tmp, [&](void *tmp, size_t &tb) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, c->bkey.p, c->bkey2.p, c->bidx.p,
+                                              c->bidx2.p, nall, 0, endbit, c->stream);
+  });
   hipLaunchKernelGGL(k_lower_bound, dim3((nqbins + 1 + 255) / 256), dim3(256), 0, c->stream,
                      nqbins, nall, 0, c->bkey2.p, c->qbeg.p);
   hipLaunchKernelGGL(k_bin_copy, dim3((nall + 255) / 256), dim3(256), 0, c->stream, nall,

@@ -331,12 +331,9 @@ inline void pc_dmass_ordered(hipStream_t s, int nins, const int *rows, const dou
   SPH_HIP_TRY(hipStreamSynchronize(s));
   SPH_REQUIRE(emitted >= 0 && emitted <= cap, SPH_HIP_EOVERFLOW,
               "fix phase_change: %d donations exceed the bound %lld", emitted, cap);
-  size_t tb = 0;
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0.p, k1.p, v0.p, v1.p, (int)cap,
-                                                 0, 64, s));
-  tmp.reserve(tb);
-  SPH_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k0.p, k1.p, v0.p, v1.p, (int)cap, 0,
-                                                 64, s));
+  with_scratch(tmp, [&](void *t, size_t &tb) {
+    return hipcub::DeviceRadixSort::SortPairs(t, tb, k0.p, k1.p, v0.p, v1.p, (int)cap, 0, 64, s);
+  });
   hipLaunchKernelGGL(k_pc_dmass_sum, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, s, cap,
                      k1.p, v1.p, dmass);
   SPH_HIP_TRY(hipGetLastError());

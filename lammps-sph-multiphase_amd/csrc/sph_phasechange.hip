@@ -51,11 +51,10 @@ int sph_hip_phasechange(sph_hip_ctx *c, const sph_phasechange_params *p, int *se
   hipLaunchKernelGGL(k_pc_flags, dim3((inum + 255) / 256), dim3(256), 0, c->stream, inum,
                      c->ilist.p, c->ty.p, c->en.p, c->cv.p, pd, flag.p);
   hipcub::CountingInputIterator<int> it(0);
-  size_t tb = 0;
-  SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flag.p, cand.p, ncand_d.p, inum, c->stream));
   DBuf<unsigned char> tmp;
-  tmp.reserve(tb);
-  SPH_HIP_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, flag.p, cand.p, ncand_d.p, inum, c->stream));
+  with_scratch(tmp, [&](void *t, size_t &tb) {
+    return hipcub::DeviceSelect::Flagged(t, tb, it, flag.p, cand.p, ncand_d.p, inum, c->stream);
+  });
   int ncand = 0;
   SPH_HIP_TRY(hipMemcpyAsync(&ncand, ncand_d.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   SPH_HIP_TRY(hipStreamSynchronize(c->stream));

@@ -71,6 +71,11 @@ struct DBuf {
     p = q;
     cap = nc;
   }
+  // a buffer that may be empty still gets an allocation (its pointer goes to kernels)
+  template <class N>
+  void reserve_min1(N n, bool keep = false, hipStream_t s = 0) {
+    reserve(n > 0 ? n : 1, keep, s);
+  }
   // grow to exactly n (no headroom): scratch twins that are swapped with a buffer of
   // capacity n keep equal capacities, so the swap never triggers a reallocation
   void reserve_exact(size_t n) {
@@ -87,6 +92,17 @@ struct DBuf {
     cap = 0;
   }
 };
+
+// A hipcub device-wide call sizes its scratch in a first call with a null scratch pointer.
+// call(void *tmp, size_t &bytes) -> hipError_t holds the one argument list: it is made for the
+// size, `scratch` grows to it, and it is made again for the work.
+template <class Call>
+void with_scratch(DBuf<unsigned char> &scratch, Call call) {
+  size_t bytes = 0;
+  SPH_HIP_TRY(call(nullptr, bytes));
+  scratch.reserve(bytes);
+  SPH_HIP_TRY(call(scratch.p, bytes));
+}
 
 void require_device(int device);
 
