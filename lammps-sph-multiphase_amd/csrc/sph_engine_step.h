@@ -1,0 +1,651 @@
+// sph_engine_step.h -- the step (Verlet::setup and Verlet::run, verlet.cpp:88-139, 222-308):
+// the pair passes over the current list (block path, row path, generic CSR kernels; the
+// multiphase stack; the passes split into interior and boundary rows behind the halos), the
+// post_force fixes (setmeso, setforce / addforce), fix dt/reset and the loop that orders them
+// with the integrates, the rebuilds and fix phase_change.
+// Writes: the forces fo / de (and rho, P in vr through the rhosum passes), the multiphase
+// passes' records and partial sums (recA .. recS, rhoS / rhoF, cgS / cgF, rho_tmp), vso / vsg,
+// the overlap's row classes (rows_in, rows_bd, n_in, n_bd, ov_ready), ff_part / ff_tot,
+// dt_rec / dt_part / h_dt, mp_flags, the nm_* counters, pc_next, step and setup_done.
+#pragma once
+#include "sph_engine_state.h"
+
+inline bool sph_engine::overlap_on() const {
+  return multi() && overlap && (blk || use_row2()) && (force_mode & M_TAIT) != 0 &&
+         cfg.rhosum_nstep > 0;
+}
+// interior rows (no ghost in the list) and boundary rows, each in row order; on the block
+// path interior and boundary BLOCKS (no ghost in the union, k_blk_interior)
+inline void sph_engine::classify_rows() {
+  const int n = nlocal;
+  if (!s2) {
+    // (a lowest-priority s2 was measured: the interior rows starve, 1.31 -> 2.17 ms per
+    // step on the loopback bench)
+    SPH_HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
+    SPH_HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    SPH_HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+  }
+  if (blk) {
+    const int nb = blk_blocks(n, blk_shape(blk_sh).R);
+    fl_in.reserve_min1(nb);
+    fl_bd.reserve_min1(nb);
+    if (nb)
+      hipLaunchKernelGGL(k_blk_interior, dim3(nb), dim3(64), 0, s, nb, ulist.p, ucnt.p,
+                         BLK_UCAP, nlocal, fl_in.p, fl_bd.p);
+    n_in = select_flagged(fl_in.p, nb, rows_in);
+    n_bd = select_flagged(fl_bd.p, nb, rows_bd);
+    SPH_REQUIRE(n_in + n_bd == nb, SPH_HIP_ERUNTIME, "block classification lost blocks");
+    ov_ready = true;
+    return;
+  }
+  fl_in.reserve_min1(n);
+  fl_bd.reserve_min1(n);
+  if (n)
+    hipLaunchKernelGGL(k_row_ghost_flags, dim3((unsigned)(((long)n * 8 + 255) / 256)),
+                       dim3(256), 0, s, n, nlocal, strided ? nullptr : off.p,
+                       strided ? list_stride : 0, ccnt.p, nbr.p, list_perm_g,
+                       (strided && list_tbits) ? 1 : 0, fl_in.p, fl_bd.p);
+  n_in = select_flagged(fl_in.p, n, rows_in);
+  n_bd = select_flagged(fl_bd.p, n, rows_bd);
+  SPH_REQUIRE(n_in + n_bd == n, SPH_HIP_ERUNTIME, "row classification lost rows");
+  ov_ready = true;
+}
+inline void sph_engine::fork() {  // s2 continues after everything queued on s so far
+  SPH_HIP_TRY(hipEventRecord(ev_fork, s));
+  SPH_HIP_TRY(hipStreamWaitEvent(s2, ev_fork, 0));
+}
+inline void sph_engine::join() {  // s continues after everything queued on s2 so far
+  SPH_HIP_TRY(hipEventRecord(ev_join, s2));
+  SPH_HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
+}
+
+// Forward comm + rhosum + forward rho + taitwater(+heat) of a non-rebuild step with the
+// halos overlapped: interior rows read no ghost, so their rhosum runs (on s2) while the
+// x/vest/rho/e halo moves, and their force pass while the rho halo moves; boundary rows
+// follow each exchange on s.  Same per-row arithmetic as pair_compute (bit-identical).
+// The forward pack may read an interior row's rho/EOS term before or after this
+// step's rhosum wrote it: ghost rho and P/rho^2 are only read after the rho halo has
+// overwritten them, so either value is harmless.
+inline void sph_engine::pair_compute_overlap() {
+  if (blk) {  // the same on the block path: interior blocks first, on s2
+    BlkArgs ka = blk_args(), ki = ka, kb = ka;
+    ki.blist = rows_in.p;
+    ki.nlist = n_in;
+    kb.blist = rows_bd.p;
+    kb.nlist = n_bd;
+    {
+      Scope t(this, T_RHO);  // (this class then includes the forward halo)
+      fork();
+      blk_rhosum(nt1(), s2, ki, xf.p, ty.p, vr.p, dc);
+      forward_multi();
+      // (the ghosts' displacement check of forward(): the interior blocks read no ghost,
+      // so whether they saw the flag before or after it is harmless)
+      if (inner && sc.x0 && nghost)
+        launch(k_inner_ghosts, nghost, nghost, nlocal, sc, xf.p);
+      blk_rhosum(nt1(), s, kb, xf.p, ty.p, vr.p, dc);
+      join();
+    }
+    {
+      Scope t(this, force_class());  // (includes the rho halo)
+      fork();
+      blk_force(nt1(), blk_visc(), force_mode, s2, ki, row_args());
+      forward_rho_multi();
+      blk_force(nt1(), blk_visc(), force_mode, s, kb, row_args());
+      join();
+    }
+    return;
+  }
+  Row2Args b = row2_args(), bi = b, bb = b;
+  bi.a.n = n_in;
+  bi.rows = rows_in.p;
+  bb.a.n = n_bd;
+  bb.rows = rows_bd.p;
+  {
+    Scope t(this, T_RHO);  // (this class then includes the forward halo)
+    fork();
+    row2_rhosum(nt1(), s2, bi);
+    forward_multi();
+    row2_rhosum(nt1(), s, bb);
+    join();
+  }
+  {
+    Scope t(this, force_class());  // (includes the rho halo)
+    fork();
+    row2_force(nt1(), row_visc(), force_mode, s2, bi);
+    forward_rho_multi();
+    row2_force(nt1(), row_visc(), force_mode, s, bb);
+    join();
+  }
+}
+
+// FixDtReset::init at setup: the record starts from cfg.dt at time 0, laststep 0
+inline void sph_engine::dt_reset_init() {
+  dt_rec.reserve(1);
+  DtRecord r{};
+  r.dt = r.dtv = cfg.dt;
+  r.dtf = sc.dtf;
+  r.brick_min = DT_BIG;
+  *h_dt = r;
+  to_dev(dt_rec.p, h_dt, 1);
+  SPH_HIP_TRY(hipStreamSynchronize(s));  // (h_dt is read back into later)
+}
+// FixDtReset::end_of_step (fix_dt_reset.cpp:131-186) of the current step: the scan over the
+// owned atoms -- with_final: behind FixMeso::final_integrate in the same pass -- and the
+// one-block fold.  One brick: two launches, nothing returns to the host.  Bricks: the fold
+// leaves this brick's minimum in the record; the host reads it back (one stream synchronise
+// per reset step, as neigh_flag_any has per check), takes the smallest over the ranks
+// (MPI_Allreduce MIN, :168; a rank without atoms takes part with BIG) and launches the
+// bounds-and-apply part with it.  The bit pattern of a positive double orders as an
+// unsigned 64-bit integer, so it travels as two allgather_int words.
+inline void sph_engine::dt_end_of_step(bool with_final) {
+  Scope t(this, T_INT);
+  const unsigned nb = blocks(nlocal);
+  dt_part.reserve_min1(nb);
+  const double *m = rm.p;
+  if (nb) {
+    if (with_final)
+      hipLaunchKernelGGL(k_dt_scan<true>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr, dt_rec.p,
+                         vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
+    else
+      hipLaunchKernelGGL(k_dt_scan<false>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr,
+                         dt_rec.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
+  }
+  if (!(multi() && tr)) {
+    hipLaunchKernelGGL(k_dt_fold<false>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
+                       (long long)step, dt_rec.p);
+    return;
+  }
+  hipLaunchKernelGGL(k_dt_fold<true>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
+                     (long long)step, dt_rec.p);
+  to_host(h_dt, dt_rec.p, 1);
+  SPH_HIP_TRY(hipStreamSynchronize(s));
+  uint64_t bits;
+  std::memcpy(&bits, &h_dt->brick_min, sizeof bits);
+  std::vector<int> hi(tr->size()), lo(tr->size());
+  tr->allgather_int((int)(uint32_t)(bits >> 32), hi.data(), s);
+  tr->allgather_int((int)(uint32_t)(bits & 0xffffffffu), lo.data(), s);
+  for (int r = 0; r < tr->size(); r++) {
+    const uint64_t b = ((uint64_t)(uint32_t)hi[r] << 32) | (uint64_t)(uint32_t)lo[r];
+    bits = std::min(bits, b);
+  }
+  double dtmin;
+  std::memcpy(&dtmin, &bits, sizeof dtmin);
+  hipLaunchKernelGGL(k_dt_apply, dim3(1), dim3(64), 0, s, dtmin, dtr, (long long)step,
+                     dt_rec.p);
+}
+
+inline RowArgs sph_engine::row_args() {
+  RowArgs a;
+  a.n = nlocal;
+  a.off = off.p;
+  a.nbr = nbr.p;
+  a.xf = xf.p;
+  a.vr = vr.p;
+  a.ty = ty.p;
+  a.en = en.p;
+  a.cf = dc;
+  a.fo = fo.p;
+  a.de = de.p;
+  a.gx = cfg.gravity[0];
+  a.gy = cfg.gravity[1];
+  a.gz = cfg.gravity[2];
+  return a;
+}
+// the generic CSR force kernels' arguments over the same arrays: every owned row of the
+// full list, gathered (no ilist, no accumulation into f, no virial)
+inline ForceArgs sph_engine::force_args() {
+  ForceArgs a{};
+  a.inum = nlocal;
+  a.nlocal = nlocal;
+  a.newton = 1;
+  a.ilist = nullptr;
+  a.off = off.p;
+  a.nbr = nbr.p;
+  a.xf = xf.p;
+  a.vr = vr.p;
+  a.ty = ty.p;
+  a.en = en.p;
+  a.fo = fo.p;
+  a.de = de.p;
+  a.accum = 0;
+  a.cf = dc;
+  a.gx = cfg.gravity[0];
+  a.gy = cfg.gravity[1];
+  a.gz = cfg.gravity[2];
+  a.virial = nullptr;
+  return a;
+}
+// extent of the list array the kernels may address
+inline int64_t sph_engine::list_span() const {
+  return strided ? (int64_t)nlocal * list_stride : nbr_total;
+}
+// entries of the current list (sum of row counts for a strided list)
+inline int64_t sph_engine::list_entries() {
+  if (!strided) return nbr_total;
+  if (nlocal == 0) return 0;
+  blen.reserve(1);
+  cub([&](void *t, size_t &tb) {
+    return hipcub::DeviceReduce::Sum(t, tb, ccnt.p, blen.p, nlocal, s);
+  });
+  long long v = 0;
+  to_host(&v, blen.p, 1);
+  SPH_HIP_TRY(hipStreamSynchronize(s));
+  return v;
+}
+inline Row2Args sph_engine::row2_args() {
+  Row2Args b;
+  b.a = row_args();
+  b.nall = nlocal + nghost;
+  b.ntot = (int)list_span();
+  if (strided) {
+    b.stride = list_stride;
+    b.rcnt = ccnt.p;
+  }
+  b.lp = row2_lp();
+  b.iv = strided && list_perm_g > 0 && list_perm_g == row2_iv_g();
+  b.exp = row2_exp();
+  b.tbits = strided && list_tbits;
+  return b;
+}
+
+// rhosum (+ the EOS epilogue) -> forward rho -> taitwater[/morris][+heat] on the current
+// list: block path, row path (row2 kernels), or the generic CSR kernels for a list past
+// the row2 kernels' 32-bit offsets.  The setup step's force pass walks the half list.
+inline void sph_engine::pair_compute(bool do_rhosum, bool setup) {
+  if (mp) {
+    pair_compute_mp();
+    return;
+  }
+  const int nall = nlocal + nghost;
+  if (do_rhosum) {
+    {
+      Scope t(this, T_RHO);
+      if (blk) {
+        blk_rhosum(nt1(), s, blk_args(), xf.p, ty.p, vr.p, dc);
+      } else if (use_row2()) {
+        row2_rhosum(nt1(), s, row2_args());
+      } else {
+        RhoArgs ra{nlocal, nullptr, off.p, nbr.p, xf.p, ty.p, vr.p, nullptr, dc};
+        launch_rhosum(cfg.dim, true, nt1(), s, ra);
+      }
+    }
+    if (multi()) {
+      Scope t(this, T_COMM);
+      forward_rho_multi();
+    } else if (nghost) {
+      Scope t(this, T_COMM);
+      launch(k_forward_rho, nghost, nghost, nlocal, gowner.p, xf.p, vr.p);
+    }
+  } else if (force_mode & M_TAIT) {
+    launch(k_eos, nall, nall, xf.p, vr.p, ty.p, dc);
+  }
+  // sph/idealgas: 0.4 e/m/rho of owned atoms and ghosts from the current e and rho (the
+  // ghosts' came with the halos), before EVERY gas pass -- e moves every step, whether or
+  // not rhosum was due
+  if ((force_mode & M_GAS) && nall)
+    launch(k_eos_gas, nall, nall, xf.p, vr.p, en.p, ty.p, dc);
+  if (force_mode && setup) {
+    setup_forces_full();
+  } else if (force_mode && blk) {
+    Scope t(this, force_class());
+    blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args());
+  } else if (force_mode && use_row2()) {
+    Scope t(this, force_class());
+    row2_force(nt1(), row_visc(), force_mode, s, row2_args());
+  } else if (force_mode) {
+    Scope t(this, force_class());
+    launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, force_args());
+  } else {
+    SPH_HIP_TRY(hipMemsetAsync(fo.p, 0, nlocal * sizeof(double4), s));
+    SPH_HIP_TRY(hipMemsetAsync(de.p, 0, nlocal * sizeof(double), s));
+  }
+}
+
+// Force pass of Verlet::setup with the reference's half-list ownership (see
+// k_half_from_full): exact even though ghost vest is stale at this point.
+// The setup step's force pass (Verlet::setup, verlet.cpp:88-139): borders() ran before
+// FixMeso::setup_pre_force, so the reference's half-list pass sees a ghost's vest as it
+// was bordered.  Walked as a full-list gather (the global-index CSR rows of the setup
+// build) that picks, for each ghost pair, the vest pair the reference's one evaluation
+// uses (k_force: vso / vsg) -- no half list, no atomics, no reverse comm.
+inline void sph_engine::setup_forces_full() {
+  const int n = nlocal, nall = nlocal + nghost;
+  if (force_mode == 0 || n == 0) return;
+  vsg.reserve_min1(nghost);
+  if (nghost)
+    dev_copy(vsg.p, vr.p + n, (size_t)nghost);
+  forward();  // the ghosts' vest as setup_pre_force left their owners' (x, rho, e unchanged)
+  fo.reserve(nall, true, s);
+  de.reserve(nall, true, s);
+  ForceArgs a = force_args();
+  a.vso = vso.p;
+  a.vsg = vsg.p;
+  launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a);
+}
+
+// ---- multiphase stack -------------------------------------------------------------
+// hybrid/overlay of bubble.lmp:57-73 in order: rhosum/multiphase and colorgradient over
+// the full list (owned rows; no forward comm of either, A.6-1), then taitwater/multiphase,
+// surfacetension and heatconduction/phasechange fused in one gather over the full list,
+// each pair in its half-list orientation (k_mp_gather: the reference's Newton-3 scatter +
+// reverse comm, without atomics or comm)
+inline void sph_engine::pair_compute_mp() {
+  const int n = nlocal, nall = nlocal + nghost;
+  fo.reserve_min1(n, true, s);
+  de.reserve_min1(n, true, s);
+  if (n == 0) return;
+  MpArgs a{};
+  a.stride = strided ? list_stride : 0;  // (else CSR: off)
+  a.cnt = ccnt.p;
+  a.inum = n;
+  a.nlocal = n;
+  a.newton = 1;
+  a.dim = cfg.dim;
+  a.ilist = nullptr;  // (rows = owned atoms)
+  a.off = off.p;
+  a.nbr = nbr.p;
+  a.xf = xf.p;
+  a.vr = vr.p;
+  a.ty = ty.p;
+  a.rm = rm.p;
+  a.en = en.p;
+  a.cv = cvv.p;
+  a.mc = dm;
+  a.typed = mp_typed_env() ? 1 : 0;  // (k_neigh3 tbits 2 writes the types)
+  // the stale version: rho and colorgradient as communicated (k_mp_gather)
+  rhoS.reserve(nall);
+  cgS.reserve(nall);
+  launch(k_mp_snap, nall, nall, vr.p, cg.p, rhoS.p, cgS.p);
+  const bool rdue = mpc.rhosum_nstep > 0 && step % mpc.rhosum_nstep == 0;
+  const bool cdue = mpc.cg_nstep > 0 && step % mpc.cg_nstep == 0;
+  {
+    Scope t(this, T_RHO);
+    if (rdue) {
+      rho_tmp.reserve(nall);
+      a.rho = rho_tmp.p;
+      if (rho_fused_step != step)  // (else the list fill of this step summed it)
+        hipLaunchKernelGGL(k_mp2_rhosum<8>, mp_rows(n), dim3(256), 0, s, a);
+      mp_flags = (mp_flags & ~SPH_STAT_MP_RHO_LISTFILL) |
+                 (rho_fused_step == step ? SPH_STAT_MP_RHO_LISTFILL : 0);
+      launch(k_mp_rho_store, n, n, rho_tmp.p, vr.p);
+    }
+    if (cdue) {
+      a.cg = cg.p;
+      recA.reserve(nall);  // (free until the force pass packs its records)
+      launch(k_mp_pack_sigma, nall, nall, xf.p, vr.p, rm.p, recA.p);
+      a.xs = recA.p;
+      hipLaunchKernelGGL(k_mp2_colorgradient<8>, mp_rows(n), dim3(256), 0, s, a);
+      a.xs = nullptr;
+    }
+  }
+  // the fresh version: the owned atoms' new values, forwarded to the ghosts
+  const double *rF = rhoS.p;
+  const double4 *cF = cgS.p;
+  if (rdue || cdue) {
+    Scope t(this, T_COMM);
+    rhoF.reserve(nall);
+    cgF.reserve(nall);
+    launch(k_mp_snap, n, n, vr.p, cg.p, rhoF.p, cgF.p);
+    forward_fresh();
+    rF = rhoF.p;
+    cF = cgF.p;
+  }
+  Scope t(this, T_TAIT);
+  if (!mpc.tait_on && !mpc.st_on)
+    SPH_HIP_TRY(hipMemsetAsync(fo.p, 0, n * sizeof(double4), s));
+  if (!mpc.heat_on) SPH_HIP_TRY(hipMemsetAsync(de.p, 0, n * sizeof(double), s));
+  MpArgs h = a;
+  h.vel = vel.p;
+  h.rhoS = rhoS.p;
+  h.rhoF = rF;
+  h.cgS = cgS.p;
+  h.cgF = cF;
+  h.fo = fo.p;
+  h.de = de.p;
+  recA.reserve(nall);
+  recK.reserve(nall);
+  recF.reserve(nall);
+  recS.reserve(nall);
+  // symmetric styles (mp2_symmetric): the issue-rate gather of sph_mp2_kernels.h
+  const bool sym = mp2_symmetric(hm);
+  if (sym)
+    launch(k_mp2_pack_rec, nall, nall, cfg.dim, xf.p, vel.p, rm.p, en.p, cvv.p, rF, rhoS.p, cF,
+           cgS.p, mpc.heat_on ? 1 : 0, recA.p, recK.p, recF.p, recS.p);
+  else
+    launch(k_mp_pack_rec, nall, nall, xf.p, vel.p, rm.p, en.p, cvv.p, rF, rhoS.p, cF, cgS.p,
+           mpc.heat_on ? 1 : 0, recA.p, recK.p, recF.p, recS.p);
+  h.pA = recA.p;
+  h.pK = recK.p;
+  h.pF = recF.p;
+  h.pS = recS.p;
+  const int sel = (mpc.tait_on ? 1 : 0) | (mpc.st_on ? 2 : 0) | (mpc.heat_on ? 4 : 0);
+  const bool g1 = mp2_gamma1(hm);
+  mp_flags = (mp_flags & SPH_STAT_MP_RHO_LISTFILL) |
+             (sel == 0 ? 0 : sym && g1 ? SPH_STAT_MP_W4 : sym ? SPH_STAT_MP_POW : SPH_STAT_MP_ROW);
+  switch (sel) {
+#define SPH_MPG(k, T, S, H)                                                                   \
+case k:                                                                                     \
+  if (sym && g1)                                                                            \
+    hipLaunchKernelGGL((k_mp2_gather_w4<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);      \
+  else if (sym)                                                                             \
+    hipLaunchKernelGGL((k_mp2_gather<8, T, S, H, true>), mp_rows(n), dim3(256), 0, s, h);   \
+  else hipLaunchKernelGGL((k_mp_gather<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);       \
+  break;
+    SPH_MPG(1, true, false, false)
+    SPH_MPG(2, false, true, false)
+    SPH_MPG(3, true, true, false)
+    SPH_MPG(4, false, false, true)
+    SPH_MPG(5, true, false, true)
+    SPH_MPG(6, false, true, true)
+    SPH_MPG(7, true, true, true)
+#undef SPH_MPG
+    default: break;
+  }
+}
+
+// single-phase engines keep no per-atom cv on the device (atom_style meso's cv takes no
+// part in its pair styles): meso_t clamps and temperature reductions take the one cv all
+// atoms were set with
+inline double sph_engine::uniform_cv(const char *who) const {
+  double c = cv_by_tag.empty() ? 1.0 : cv_by_tag[0];
+  for (double v : cv_by_tag)
+    SPH_REQUIRE(v == c, SPH_HIP_EINVAL,
+                "%s on a single-phase engine needs one cv for all atoms (got %g and %g); "
+                "per-atom cv is the multiphase engine's",
+                who, c, v);
+  return c;
+}
+
+// FixSetMeso / FixSetMesodE post_force of the armed clamps on the owned rows: one launch,
+// none without a clamp
+inline void sph_engine::post_force_setmeso() {
+  if (sm.nfix == 0 || nlocal == 0) return;
+  Scope t(this, T_INT);
+  const double cvc = (!mp && sm_needs_cv) ? uniform_cv("fix setmeso meso_t") : 1.0;
+  launch(k_setmeso, nlocal, nlocal, sm, xf.p, vr.p, en.p, de.p, ty.p,
+         mp ? (const double *)cvv.p : nullptr, cvc,
+         (!mp && (force_mode & M_TAIT)) ? (const Coefs *)dc : nullptr);
+}
+
+// the types' masses as configured (sc.mass is the body-force mass: 0 outside gravity_mask)
+inline StepMass sph_engine::type_mass() const {
+  StepMass m;
+  for (int t = 0; t <= MAXT; t++) m.mass[t] = cfg.mass[t];
+  return m;
+}
+
+// FixSetForce / FixAddForce post_force of the armed fixes that are due in this step
+// (ntimestep % nevery == 0) on the owned rows, after the pair compute has left f whole:
+// the tallying fixes' foriginal sums first (k_forcefix_tally reads f as the chain finds
+// it), then one launch of k_forcefix; none without a due fix
+inline void sph_engine::post_force_forcefix() {
+  if (ff.nfix == 0) return;
+  ForceFixArgs a = ff;
+  a.active = 0;
+  bool tally = false;
+  for (int k = 0; k < ff.nfix; k++)
+    if (step % ff.fix[k].nevery == 0) {
+      a.active |= 1 << k;
+      tally = tally || ff.fix[k].tally;
+    }
+  if (a.active == 0) return;
+  Scope t(this, T_INT);
+  const StepMass tm = type_mass();
+  const double *m = mp ? (const double *)rm.p : nullptr;
+  if (tally) {
+    const int nb = (int)std::min<long>(blocks(nlocal), RED_MAXBLOCKS);
+    ff_part.reserve((size_t)RED_MAXBLOCKS * FF_NT);
+    if (nb)
+      hipLaunchKernelGGL(k_forcefix_tally, dim3(nb), dim3(RED_THREADS), 0, s, nlocal, a, xf.p,
+                         ty.p, m, tm, fo.p, ff_part.p);
+    hipLaunchKernelGGL(k_forcefix_final, dim3(1), dim3(64), 0, s, nb, a, ff_part.p, ff_tot.p);
+  }
+  if (nlocal)
+    launch(k_forcefix, nlocal, nlocal, a, xf.p, ty.p, m, tm, fo.p);
+}
+
+inline bool sph_engine::rhosum_due() const {
+  return cfg.rhosum_nstep > 0 && (step % cfg.rhosum_nstep) == 0;
+}
+
+// Verlet::setup (verlet.cpp:88-139)
+inline void sph_engine::setup() {
+  step = 0;
+  Scope t(this, T_NEIGH);
+  if (pc) {  // (every setup sorts: verlet.cpp:106)
+    if (!lidx_valid) lidx_from_tags();
+    nextsort = 0;
+  }
+  // borders() runs before setup_pre_force: ghosts carry vest as it was (reference order);
+  // the setup force pass needs the global-index list for its half-list walk
+  build_all(true);
+  vso.reserve_min1(nlocal);  // (vest before setup_pre_force: setup_forces_full)
+  if (nlocal)
+    dev_copy(vso.p, vr.p, (size_t)nlocal);
+  launch(k_vest_from_v, nlocal, nlocal, cfg.stationary_mask, ty.p, vel.p, vr.p);
+  pair_compute(rhosum_due(), /*setup=*/true);
+  post_force_setmeso();  // (FixSetMeso::setup calls post_force)
+  if (ff_tally) {
+    ff_tot.reserve(FF_NT);
+    SPH_HIP_TRY(hipMemsetAsync(ff_tot.p, 0, FF_NT * sizeof(double), s));
+  }
+  post_force_forcefix();  // (FixSetForce::setup / FixAddForce::setup too)
+  nm_builds = nm_danger = nm_checks = 0;
+  neigh_built();  // (Neighbor::ncalls counts the setup's build)
+  if (dtr_on) {  // FixDtReset::setup = end_of_step, after every post_force fix's own setup
+    dt_reset_init();
+    dt_end_of_step(false);
+  }
+  setup_done = true;
+}
+
+// The step's integrate launch of an engine with fix dt/reset: the same kernels in their
+// instantiations that take {dtv, dtf} from the device record.  alone: the previous step's
+// final integrate has run already (the first step of a run, or the step after a reset step).
+inline void sph_engine::integrate_dt(bool alone, bool chk) {
+  Scope t(this, T_INT);
+  const DtFrom<true> dr{&dt_rec.p->dtv};
+  const dim3 g(blocks(nlocal)), b(BLK);
+  if (chk) {
+    const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
+    if (alone)
+      hipLaunchKernelGGL((k_initial_integrate<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                         en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
+    else
+      hipLaunchKernelGGL((k_final_initial<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                         en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
+  } else if (alone) {
+    hipLaunchKernelGGL((k_initial_integrate<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
+                       en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
+  } else {
+    hipLaunchKernelGGL((k_final_initial<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p, en.p,
+                       ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
+  }
+}
+
+// Verlet::run (verlet.cpp:222-308)
+inline void sph_engine::run(int nsteps) {
+  // the final_integrate of step k-1 runs fused with the initial_integrate of step k;
+  // the last step's final_integrate runs on its own after the loop
+  bool final_done = false;  // (fix dt/reset: the step's final integrate has run already)
+  for (int k = 0; k < nsteps; k++) {
+    step++;
+    if (sc.x0) sc.moved = moved_flag();
+    // Neighbor::decide (neighbor.cpp:1332-1410).  A due fix phase_change is must_check: it
+    // builds before ago counts.  Otherwise ago counts, and the step is eligible once
+    // ago >= delay && ago % every == 0 -- known before the integrate is launched, so only
+    // an eligible step of a check-yes engine runs the checking instantiation.  (The box
+    // never changes in the engine: the reference's boxcheck branch does not apply.)
+    const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
+    const bool elig = !pc_due && neigh_eligible(nm_ago + 1);
+    const bool chk = elig && nm_check;
+    if (dtr_on) {
+      integrate_dt(k == 0 || final_done, chk);
+    } else {
+      Scope t(this, T_INT);
+      if (chk) {
+        const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
+        if (k == 0)
+          launch((k_initial_integrate<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+                 vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
+        else
+          launch((k_final_initial<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+                 vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
+      } else if (k == 0) {
+        launch((k_initial_integrate<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
+               vel.p, fo.p, de.p, rm.p, StepOpt<false, false>{});
+      } else {
+        launch((k_final_initial<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p,
+               fo.p, de.p, rm.p, StepOpt<false, false>{});
+      }
+    }
+    bool build = pc_due;
+    if (!pc_due) {
+      nm_ago++;
+      if (chk) {
+        nm_checks++;
+        build = neigh_flag_any();
+        // (a check that fires at its first opportunity, neighbor.cpp:1408)
+        if (build && nm_ago == std::max(neigh_every(), nm_delay)) nm_danger++;
+      } else {
+        build = elig;
+      }
+    }
+    if (pc_due) {
+      phase_change();
+      pc_next += pc_nevery;
+    }
+    if (build) {
+      rebuild();
+      neigh_built();
+      pair_compute(rhosum_due());
+    } else if (ov_ready && rhosum_due() && overlap_on()) {
+      pair_compute_overlap();
+    } else {
+      forward();
+      pair_compute(rhosum_due());
+    }
+    post_force_setmeso();
+    post_force_forcefix();
+    // (check yes: whether the next step rebuilds is not known yet -- a refresh that a
+    // rebuild then supersedes is harmless, the rebuild clears both slots)
+    refresh_inner(nm_check ? (pc && step + 1 == pc_next) : (!pc && neigh_eligible(nm_ago + 1)));
+    if (timing && pending.size() > 4096) harvest();
+    // fix dt/reset: Modify::end_of_step follows the final integrate of a step with
+    // ntimestep % nevery == 0 (modify.cpp:404-408, verlet.cpp:299), and the next initial
+    // integrate needs the dt it leaves: the final integrate runs here with the scan behind
+    // it, then the fold, and the next step (or the next run) integrates on its own -- three
+    // launches where the other steps have the fused one
+    final_done = dtr_on && step % dtr_nevery == 0;
+    if (final_done) dt_end_of_step(true);
+  }
+  if (nsteps > 0 && !final_done) {
+    Scope t(this, T_INT);
+    if (dtr_on)
+      launch(k_final_integrate_dt, nlocal, nlocal, sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p,
+             DtFrom<true>{&dt_rec.p->dtv});
+    else
+      launch(k_final_integrate, nlocal, nlocal, sc, vr.p, en.p, ty.p, vel.p, fo.p, de.p, rm.p);
+  }
+  SPH_HIP_TRY(hipGetLastError());
+}

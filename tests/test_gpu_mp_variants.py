@@ -1,4 +1,4 @@
-"""The device-resident engine's multiphase pass (pair_compute_mp, csrc/sph_engine.hip) on
+"""The device-resident engine's multiphase pass (pair_compute_mp, csrc/sph_engine_step.h) on
 jittered two- and three-phase boxes, every gather family and style subset, under the strict
 bar of mp_variants_util (1e-10 normwise and per element, the oracle's reordering / one-ulp
 spread only, exact zeros where the oracle's field is zero).
