@@ -35,6 +35,7 @@
 
 #include "sph_engine_kernels.h"
 #include "sph_row2_kernels.h"
+#include "sph_select.h"
 #include "sph_util.h"
 
 namespace sph {
@@ -99,7 +100,7 @@ __device__ __forceinline__ unsigned writelane(unsigned v, unsigned val) {
 // for S slots) and decodes s from q.
 constexpr int BLK_CH = 1024, BLK_CHE = 1280;
 // the force pass's VISC for one type with Monaghan viscosity and viscC = 0 (no viscosity
-// term; the engine selects it, sph_engine.hip force_pass)
+// term; the engine selects it, sph_engine::blk_visc in sph_engine_state.h)
 constexpr int BLK_VISC_NONE = 2;
 __host__ __device__ inline int blk_q(int s, int cq) { return (s >> 4) * cq + (s & 15); }
 template <int CQ>
@@ -1566,15 +1567,10 @@ k_blk_stats(int nb, const int *__restrict__ ucnt, const int *__restrict__ kcnt,
 #else
 #define SPH_BLK_SHAPES(X) X(0, 64, 8, 4) X(1, 32, 8, 4)
 #endif
-constexpr int BLK_NCH = 8;  // slot chunks preloaded per row (rows up to BLK_NCH*U*G entries)
 // The pair passes walk a row's chunks of U * G entries in steps of G (the transposed layout,
 // blk_tpos, ties the walk's U to the build's; round 3's 16-entry chunks with U = 2 were
 // slower, profiles/r03/README.md)
-template <int U>
-struct BlkWalk {
-  static constexpr int UW = U;
-  static constexpr int NCH = BLK_NCH;
-};
+constexpr int BLK_NCH = 8;  // slot chunks preloaded per row (rows up to BLK_NCH*U*G entries)
 struct BlkShape {
   int R, G, U;
 };
@@ -1631,171 +1627,122 @@ k_blk_interior(int nb, const int *__restrict__ ulist, const int *__restrict__ uc
 
 inline int blk_blocks(int n, int R) { return (n + R - 1) / R; }
 
-template <int R, int G, int U, int MC>
-inline void blk_neigh_t(bool nt1, hipStream_t s, int n, const QBins &q, int dim,
-                        const double4 *xf, const int *ty, const double4 *xb, const int *tb,
-                        const int *qbeg, const int *xpos, const Coefs *cf, int ucap,
-                        int sstride, int *ulist, int *ucnt, int *rcnt, unsigned short *snbr,
-                        int *ovf, int *umax, int cq, int bexp) {
-  if (nt1)
-    hipLaunchKernelGGL((k_blk_neigh<R, G, U, true, MC>), dim3(blk_blocks(n, R)),
-                       dim3(R * BLK_TPR), 0, s, n, q, dim, xf, ty, xb, tb, qbeg, xpos, cf, ucap,
-                       sstride, ulist, ucnt, rcnt, snbr, ovf, umax, cq, bexp);
-  else
-    hipLaunchKernelGGL((k_blk_neigh<R, G, U, false, MC>), dim3(blk_blocks(n, R)),
-                       dim3(R * BLK_TPR), 0, s, n, q, dim, xf, ty, xb, tb, qbeg, xpos, cf, ucap,
-                       sstride, ulist, ucnt, rcnt, snbr, ovf, umax, cq, bexp);
-}
+// The launchers below turn their run-time selectors into template arguments with the helpers
+// of sph_select.h; each kernel's argument list stands at one hipLaunchKernelGGL.
+// f(Dims<R, G, U>{}) of block shape k; nothing for a shape the table does not list
+SPH_SHAPE_SELECT(blk_select_shape, SPH_BLK_SHAPES)
+
+// the arguments of a block build, k_blk_build or k_blk_neigh (host side: a launch unpacks
+// them into its kernel's order)
+struct BlkBuildArgs {
+  int n = 0;  // owned rows
+  QBins q{};
+  int dim = 3;
+  const double4 *xf = nullptr;
+  const int *ty = nullptr;
+  const double4 *xb = nullptr;  // the bin-sorted copy, its types and the bins' offsets into it
+  const int *tb = nullptr, *qbeg = nullptr;
+  const Coefs *cf = nullptr;
+  int ucap = 0, sstride = 0;  // union stride of ulist, slot-row stride
+  int *ulist = nullptr, *ucnt = nullptr, *rcnt = nullptr;
+  unsigned short *snbr = nullptr;
+  int *ovf = nullptr, *umax = nullptr;  // the overflow word and the statistics words
+  int cq = BLK_CH / 16;
+  int bexp = 0;  // study variants (SPH_BEXP), 0 in production
+  // k_blk_neigh only
+  const int *xpos = nullptr;
+  // k_blk_build only: the inner rows and their union (uilist == nullptr: over the full one),
+  // the blocks' kept candidates, and the small candidate image (BLK_SCAP_S)
+  int *icnt = nullptr;
+  unsigned short *snbi = nullptr;
+  int *uilist = nullptr, *uicnt = nullptr, *kcnt = nullptr;
+  bool small = false;
+};
+
+// k_blk_neigh (the bitmap walk: the large-image fallback of k_blk_build)
 // big: the large candidate image (BLK_MBIG; 32-row shapes only)
-inline void blk_neigh(int shape, bool big, bool nt1, hipStream_t s, int n, const QBins &q,
-                      int dim, const double4 *xf, const int *ty, const double4 *xb,
-                      const int *tb, const int *qbeg, const int *xpos, const Coefs *cf,
-                      int ucap, int sstride, int *ulist, int *ucnt, int *rcnt,
-                      unsigned short *snbr, int *ovf, int *umax, int cq, int bexp = 0) {
-  switch (shape) {
-#define SPH_CASE(k, R, G, U)                                                                \
-  case k:                                                                                 \
-    if (big && R == 32)                                                                   \
-      blk_neigh_t<R, G, U, BLK_MBIG>(nt1, s, n, q, dim, xf, ty, xb, tb, qbeg, xpos, cf,   \
-                                     ucap, sstride, ulist, ucnt, rcnt, snbr, ovf, umax, cq, bexp); \
-    else                                                                                  \
-      blk_neigh_t<R, G, U, BLK_MCAP>(nt1, s, n, q, dim, xf, ty, xb, tb, qbeg, xpos, cf,   \
-                                     ucap, sstride, ulist, ucnt, rcnt, snbr, ovf, umax, cq, bexp); \
-    break;
-    SPH_BLK_SHAPES(SPH_CASE)
-#undef SPH_CASE
-  }
+inline void blk_neigh(int shape, bool big, bool nt1, hipStream_t s, const BlkBuildArgs &a) {
+  blk_select_shape(shape, [&](auto sh) {
+    constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2];
+    select_bool(big && R == 32, [&](auto bg) {
+      constexpr int MC = bg ? BLK_MBIG : BLK_MCAP;
+      select_bool(nt1, [&](auto t) {
+        constexpr bool NT1 = t;
+        hipLaunchKernelGGL((k_blk_neigh<R, G, U, NT1, MC>), dim3(blk_blocks(a.n, R)),
+                           dim3(R * BLK_TPR), 0, s, a.n, a.q, a.dim, a.xf, a.ty, a.xb, a.tb,
+                           a.qbeg, a.xpos, a.cf, a.ucap, a.sstride, a.ulist, a.ucnt, a.rcnt,
+                           a.snbr, a.ovf, a.umax, a.cq, a.bexp);
+      });
+    });
+  });
 }
 
-// k_blk_build (the default block build; k_blk_neigh remains the large-image fallback)
-template <int R, int G, int U, bool NT1, bool INNER>
-inline void blk_build_t(hipStream_t s, int n, const QBins &q, int dim, const double4 *xf,
-                        const int *ty, const double4 *xb, const int *tb, const int *qbeg,
-                        const Coefs *cf, int ucap, int sstride, int *ulist, int *ucnt,
-                        int *rcnt, unsigned short *snbr, int *icnt, unsigned short *snbi,
-                        int *ovf, int *umax, int cq, int bexp, int *uilist, int *uicnt,
-                        int *kcnt) {
-  // (bexp bit 8: the small candidate image, BLK_SCAP_S)
-  const bool small = (bexp & 0x100) != 0;
-  bexp &= 0xff;
-#ifdef SPH_STUDY
-  auto fn = bexp == 1 ? k_blk_build<R, G, U, NT1, INNER, 1>
-          : bexp == 2 ? k_blk_build<R, G, U, NT1, INNER, 2>
-          : bexp == 3 ? k_blk_build<R, G, U, NT1, INNER, 3>
-          : bexp == 4 ? k_blk_build<R, G, U, NT1, INNER, 4>
-          : small     ? k_blk_build<R, G, U, NT1, INNER, 0, BLK_SCAP_S>
-                      : k_blk_build<R, G, U, NT1, INNER, 0>;
-#else
-  auto fn = small ? k_blk_build<R, G, U, NT1, INNER, 0, BLK_SCAP_S>
-                  : k_blk_build<R, G, U, NT1, INNER, 0>;
-#endif
-  hipLaunchKernelGGL(fn, dim3(blk_blocks(n, R)), dim3(256), 0, s, n, q, dim, xf, ty, xb, tb,
-                     qbeg, cf, ucap, sstride, ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq,
-                     uilist, uicnt, kcnt);
-  hipLaunchKernelGGL(k_blk_stats, dim3(1), dim3(1024), 0, s, blk_blocks(n, R), ucnt, kcnt,
-                     uicnt, umax);
-}
-template <int R, int G, int U>
-inline void blk_build_s(bool nt1, bool inner, hipStream_t s, int n, const QBins &q, int dim,
-                        const double4 *xf, const int *ty, const double4 *xb, const int *tb,
-                        const int *qbeg, const Coefs *cf, int ucap, int sstride, int *ulist,
-                        int *ucnt, int *rcnt, unsigned short *snbr, int *icnt,
-                        unsigned short *snbi, int *ovf, int *umax, int cq, int bexp,
-                        int *uilist, int *uicnt, int *kcnt) {
-  if (nt1 && inner)
-    blk_build_t<R, G, U, true, true>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                     ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
-                                     uilist, uicnt, kcnt);
-  else if (nt1)
-    blk_build_t<R, G, U, true, false>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                      ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
-                                      uilist, uicnt, kcnt);
-  else if (inner)
-    blk_build_t<R, G, U, false, true>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                      ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
-                                      uilist, uicnt, kcnt);
-  else
-    blk_build_t<R, G, U, false, false>(s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride,
-                                       ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp,
-                                       uilist, uicnt, kcnt);
-}
-inline void blk_build(int shape, bool nt1, bool inner, hipStream_t s, int n, const QBins &q,
-                      int dim, const double4 *xf, const int *ty, const double4 *xb,
-                      const int *tb, const int *qbeg, const Coefs *cf, int ucap, int sstride,
-                      int *ulist, int *ucnt, int *rcnt, unsigned short *snbr, int *icnt,
-                      unsigned short *snbi, int *ovf, int *umax, int cq, int bexp, int *uilist,
-                      int *uicnt, int *kcnt) {
-  switch (shape) {
-#define SPH_CASE(k, R, G, U)                                                                 \
-  case k:                                                                                  \
-    blk_build_s<R, G, U>(nt1, inner, s, n, q, dim, xf, ty, xb, tb, qbeg, cf, ucap, sstride, \
-                         ulist, ucnt, rcnt, snbr, icnt, snbi, ovf, umax, cq, bexp, uilist,   \
-                         uicnt, kcnt);                                                       \
-    break;
-    SPH_BLK_SHAPES(SPH_CASE)
-#undef SPH_CASE
-  }
+// k_blk_build (the default block build; k_blk_neigh remains the large-image fallback), and
+// k_blk_stats over its per-block counts directly behind it
+inline void blk_build(int shape, bool nt1, bool inner, hipStream_t s, const BlkBuildArgs &a) {
+  blk_select_shape(shape, [&](auto sh) {
+    constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2];
+    select_bool(nt1, [&](auto t) {
+      constexpr bool NT1 = t;
+      select_bool(inner, [&](auto in) {
+        constexpr bool INNER = in;
+        auto launch = [&](auto be, auto sm) {
+          constexpr int BEXP = be;
+          // the small candidate image exists only without a study variant
+          constexpr int SC = (sm && BEXP == 0) ? BLK_SCAP_S : BLK_SCAP;
+          hipLaunchKernelGGL((k_blk_build<R, G, U, NT1, INNER, BEXP, SC>),
+                             dim3(blk_blocks(a.n, R)), dim3(256), 0, s, a.n, a.q, a.dim, a.xf,
+                             a.ty, a.xb, a.tb, a.qbeg, a.cf, a.ucap, a.sstride, a.ulist, a.ucnt,
+                             a.rcnt, a.snbr, a.icnt, a.snbi, a.ovf, a.umax, a.cq, a.uilist,
+                             a.uicnt, a.kcnt);
+          hipLaunchKernelGGL(k_blk_stats, dim3(1), dim3(1024), 0, s, blk_blocks(a.n, R), a.ucnt,
+                             a.kcnt, a.uicnt, a.umax);
+        };
+        select_bool(a.small, [&](auto sm) {
+          // (BEXP: outputs meaningless, study builds only, make STUDY=1)
+          if constexpr (STUDY_BUILD)
+            select_int<0, 1, 2, 3, 4>(a.bexp, [&](auto be) { launch(be, sm); });
+          else
+            launch(std::integral_constant<int, 0>{}, sm);
+        });
+      });
+    });
+  });
 }
 
-template <int R, int G, int U, int NCH, bool NT1>
-inline void blk_rhosum_t(hipStream_t s, const BlkArgs &k, double4 *xf, const int *ty,
-                         double4 *vr, const Coefs *cf) {
-  const size_t lds = blk_rho_lds(k.um, NT1);
-  auto fn = k.cq == BLK_CH / 16 ? k_blk_rhosum<R, G, U, NCH, NT1, BLK_CH / 16>
-                                : k_blk_rhosum<R, G, U, NCH, NT1, BLK_CHE / 16>;
-  SPH_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  const int nb = k.blist ? k.nlist : blk_blocks(k.n, R);
-  if (nb == 0) return;
-  hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt,
-                     k.ucap, k.snbr, k.sstride, k.rcnt, xf, ty, vr, cf, k.um, k.snbi, k.icnt,
-                     k.moved, k.uilist, k.uicnt, k.blist);
+// f(Dims<R, G, U>{}, NT1, NCH): the selectors the three pair passes share.  NCH = BLK_NCH
+// where the build's rows fit the chunks a lane preloads (BlkArgs::pre), else 0: long rows,
+// walked with a prefetch (BlkSlots)
+template <class F>
+inline void blk_select(bool nt1, const BlkArgs &k, F &&f) {
+  blk_select_shape(k.shape, [&](auto sh) {
+    select_bool(nt1, [&](auto t) {
+      select_bool(k.pre(BlkShape{sh.v[0], sh.v[1], sh.v[2]}), [&](auto pre) {
+        f(sh, t, std::integral_constant<int, pre ? BLK_NCH : 0>{});
+      });
+    });
+  });
 }
-template <int R, int G, int U>
-inline void blk_rhosum_s(bool nt1, hipStream_t s, const BlkArgs &k, double4 *xf, const int *ty,
-                         double4 *vr, const Coefs *cf) {
-  const bool pre = k.pre(BlkShape{R, G, U});
-  constexpr int UW = BlkWalk<U>::UW, NW = BlkWalk<U>::NCH;
-  if (nt1) {
-    if (pre) blk_rhosum_t<R, G, UW, NW, true>(s, k, xf, ty, vr, cf);
-    else blk_rhosum_t<R, G, U, 0, true>(s, k, xf, ty, vr, cf);
-  } else {
-    if (pre) blk_rhosum_t<R, G, UW, NW, false>(s, k, xf, ty, vr, cf);
-    else blk_rhosum_t<R, G, U, 0, false>(s, k, xf, ty, vr, cf);
-  }
-}
+
 inline void blk_rhosum(bool nt1, hipStream_t s, const BlkArgs &k, double4 *xf, const int *ty,
                        double4 *vr, const Coefs *cf) {
   if (k.n == 0) return;
-  switch (k.shape) {
-#define SPH_CASE(q, R, G, U) \
-  case q: blk_rhosum_s<R, G, U>(nt1, s, k, xf, ty, vr, cf); break;
-    SPH_BLK_SHAPES(SPH_CASE)
-#undef SPH_CASE
-  }
-}
-
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
-inline void blk_force_t(hipStream_t s, const BlkArgs &k, const RowArgs &a) {
-  auto fn = [] {
-    if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0)
-      return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP>;
-    else
-      return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP>;
-  }();
-  // one launch: every block, its union in windows of umf records where it exceeds the image
-  size_t lds = blk_lds(k.umf, k.cq, NT1);
-#ifdef SPH_STUDY  // (SPH_LDS_PAD: extra LDS per workgroup, an occupancy study)
-  if (const char *e = getenv("SPH_LDS_PAD")) lds += (size_t)atoi(e);
-#endif
-  SPH_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  const int nb = k.blist ? k.nlist : blk_blocks(k.n, R);
-  if (nb == 0) return;
-  hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt,
-                     k.ucap, k.snbr, k.sstride, k.rcnt, a.xf, a.vr, a.ty, a.en, a.cf, a.fo,
-                     a.de, a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved, k.uilist,
-                     k.uicnt, k.blist);
+  blk_select(nt1, k, [&](auto sh, auto t, auto nch) {
+    constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2], NCH = nch;
+    constexpr bool NT1 = t;
+    select_int<BLK_CHE / 16, BLK_CH / 16>(k.cq, [&](auto cq) {
+      constexpr int CQ = cq;
+      auto fn = k_blk_rhosum<R, G, U, NCH, NT1, CQ>;
+      const size_t lds = blk_rho_lds(k.um, NT1);
+      SPH_HIP_TRY(hipFuncSetAttribute((const void *)fn,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const int nb = k.blist ? k.nlist : blk_blocks(k.n, R);
+      if (nb == 0) return;
+      hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt, k.ucap, k.snbr,
+                         k.sstride, k.rcnt, xf, ty, vr, cf, k.um, k.snbi, k.icnt, k.moved,
+                         k.uilist, k.uicnt, k.blist);
+    });
+  });
 }
 
 // the inner rows of a build (k_blk_inner): same launch geometry and LDS image as rhosum
@@ -1807,89 +1754,74 @@ struct BlkInnerRefresh {
   double4 *x0 = nullptr;
   int *umax = nullptr;  // (the inner unions' largest and sum, as k_blk_build's umax + 6, 7)
 };
-template <int R, int G, int U, int NCH, bool NT1>
-inline void blk_inner_t(hipStream_t s, const BlkArgs &k, const double4 *xf, const int *ty,
-                        const Coefs *cf, unsigned short *snbi, int *icnt,
-                        const BlkInnerRefresh &rf) {
-  const size_t lds = blk_rho_lds(k.um, NT1);
-  auto fn = k.cq == BLK_CH / 16 ? k_blk_inner<R, G, U, NCH, NT1, BLK_CH / 16>
-                                : k_blk_inner<R, G, U, NCH, NT1, BLK_CHE / 16>;
-  SPH_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  const int nb = blk_blocks(k.n, R);
-  hipLaunchKernelGGL(fn, dim3(rf.cond ? std::min(nb, 512) : nb), dim3(R * G), lds, s, k.n,
-                     k.ulist, k.ucnt, k.ucap, k.snbr, k.sstride, k.rcnt, xf, ty, cf, snbi, icnt,
-                     k.um, rf.cond, rf.zero, rf.x0, k.uilist, k.uicnt, rf.umax);
-}
-template <int R, int G, int U>
-inline void blk_inner_s(bool nt1, hipStream_t s, const BlkArgs &k, const double4 *xf,
-                        const int *ty, const Coefs *cf, unsigned short *snbi, int *icnt,
-                        const BlkInnerRefresh &rf) {
-  const bool pre = k.pre(BlkShape{R, G, U});
-  if (nt1) {
-    if (pre) blk_inner_t<R, G, U, BLK_NCH, true>(s, k, xf, ty, cf, snbi, icnt, rf);
-    else blk_inner_t<R, G, U, 0, true>(s, k, xf, ty, cf, snbi, icnt, rf);
-  } else {
-    if (pre) blk_inner_t<R, G, U, BLK_NCH, false>(s, k, xf, ty, cf, snbi, icnt, rf);
-    else blk_inner_t<R, G, U, 0, false>(s, k, xf, ty, cf, snbi, icnt, rf);
-  }
-}
 inline void blk_inner(bool nt1, hipStream_t s, const BlkArgs &k, const double4 *xf,
                       const int *ty, const Coefs *cf, unsigned short *snbi, int *icnt,
                       const BlkInnerRefresh &rf = BlkInnerRefresh{}) {
   if (k.n == 0) return;
-  switch (k.shape) {
-#define SPH_CASE(q, R, G, U) \
-  case q: blk_inner_s<R, G, U>(nt1, s, k, xf, ty, cf, snbi, icnt, rf); break;
-    SPH_BLK_SHAPES(SPH_CASE)
-#undef SPH_CASE
-  }
+  blk_select(nt1, k, [&](auto sh, auto t, auto nch) {
+    constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2], NCH = nch;
+    constexpr bool NT1 = t;
+    select_int<BLK_CHE / 16, BLK_CH / 16>(k.cq, [&](auto cq) {
+      constexpr int CQ = cq;
+      auto fn = k_blk_inner<R, G, U, NCH, NT1, CQ>;
+      const size_t lds = blk_rho_lds(k.um, NT1);
+      SPH_HIP_TRY(hipFuncSetAttribute((const void *)fn,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const int nb = blk_blocks(k.n, R);
+      hipLaunchKernelGGL(fn, dim3(rf.cond ? std::min(nb, 512) : nb), dim3(R * G), lds, s, k.n,
+                         k.ulist, k.ucnt, k.ucap, k.snbr, k.sstride, k.rcnt, xf, ty, cf, snbi,
+                         icnt, k.um, rf.cond, rf.zero, rf.x0, k.uilist, k.uicnt, rf.umax);
+    });
+  });
 }
-template <int R, int G, int U, int NCH, bool NT1>
-inline void blk_force_n(int visc, int mode, hipStream_t s, const BlkArgs &k, const RowArgs &a) {
-  const bool mor = visc == SPH_VISC_MORRIS;
-  switch (mode) {
-    case M_TAIT:
-      if (mor) blk_force_t<R, G, U, NCH, 1, M_TAIT, NT1>(s, k, a);
-      else if (NT1 && visc == BLK_VISC_NONE)
-        blk_force_t<R, G, U, NCH, BLK_VISC_NONE, M_TAIT, NT1>(s, k, a);
-#ifdef SPH_STUDY  // (outputs meaningless: study builds only, make STUDY=1)
-      else if (NT1 && k.exp == 1) blk_force_t<R, G, U, NCH, 0, M_TAIT, NT1, 1>(s, k, a);
-      else if (NT1 && k.exp == 2) blk_force_t<R, G, U, NCH, 0, M_TAIT, NT1, 2>(s, k, a);
-      else if (NT1 && k.exp == 3) blk_force_t<R, G, U, NCH, 0, M_TAIT, NT1, 3>(s, k, a);
-#endif
-      else blk_force_t<R, G, U, NCH, 0, M_TAIT, NT1>(s, k, a);
-      break;
-    case M_TAIT | M_HEAT:
-      if (mor) blk_force_t<R, G, U, NCH, 1, M_TAIT | M_HEAT, NT1>(s, k, a);
-      else blk_force_t<R, G, U, NCH, 0, M_TAIT | M_HEAT, NT1>(s, k, a);
-      break;
-    case M_GAS: blk_force_t<R, G, U, NCH, 0, M_GAS, NT1>(s, k, a); break;
-    default: blk_force_t<R, G, U, NCH, 0, M_HEAT, NT1>(s, k, a); break;
-  }
-}
-template <int R, int G, int U>
-inline void blk_force_s(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs &k,
-                        const RowArgs &a) {
-  const bool pre = k.pre(BlkShape{R, G, U});
-  constexpr int UW = BlkWalk<U>::UW, NW = BlkWalk<U>::NCH;
-  if (nt1) {
-    if (pre) blk_force_n<R, G, UW, NW, true>(visc, mode, s, k, a);
-    else blk_force_n<R, G, U, 0, true>(visc, mode, s, k, a);
-  } else {
-    if (pre) blk_force_n<R, G, UW, NW, false>(visc, mode, s, k, a);
-    else blk_force_n<R, G, U, 0, false>(visc, mode, s, k, a);
-  }
-}
+
 inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs &k,
                       const RowArgs &a) {
   if (k.n == 0) return;
-  switch (k.shape) {
-#define SPH_CASE(q, R, G, U) \
-  case q: blk_force_s<R, G, U>(nt1, visc, mode, s, k, a); break;
-    SPH_BLK_SHAPES(SPH_CASE)
-#undef SPH_CASE
-  }
+  // BLK_VISC_NONE and the study variants are for one type
+  const int visc1 = (visc == BLK_VISC_NONE && !nt1) ? SPH_VISC_MONAGHAN : visc;
+  const int exp1 = nt1 ? k.exp : 0;
+  blk_select(nt1, k, [&](auto sh, auto t, auto nch) {
+    constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2], NCH = nch;
+    constexpr bool NT1 = t;
+    select_int<M_HEAT, M_TAIT, M_TAIT | M_HEAT, M_GAS>(mode, [&](auto m) {
+      constexpr int MODE = m;
+      select_int<SPH_VISC_MONAGHAN, SPH_VISC_MORRIS, BLK_VISC_NONE>(visc1, [&](auto vc) {
+        // Morris viscosity exists only for the modes with M_TAIT, BLK_VISC_NONE only for
+        // M_TAIT alone
+        constexpr int VISC = (MODE == M_TAIT || (vc == SPH_VISC_MORRIS && (MODE & M_TAIT)))
+                                 ? (int)vc : SPH_VISC_MONAGHAN;
+        auto launch = [&](auto ex) {
+          constexpr int EXP = ex;
+          auto fn = [] {
+            if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0)
+              return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP>;
+            else
+              return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP>;
+          }();
+          // one launch: every block, its union in windows of umf records where it exceeds
+          // the image
+          size_t lds = blk_lds(k.umf, k.cq, NT1);
+#ifdef SPH_STUDY  // (SPH_LDS_PAD: extra LDS per workgroup, an occupancy study)
+          if (const char *e = getenv("SPH_LDS_PAD")) lds += (size_t)atoi(e);
+#endif
+          SPH_HIP_TRY(hipFuncSetAttribute(
+              (const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          const int nb = k.blist ? k.nlist : blk_blocks(k.n, R);
+          if (nb == 0) return;
+          hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt, k.ucap,
+                             k.snbr, k.sstride, k.rcnt, a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de,
+                             a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved, k.uilist,
+                             k.uicnt, k.blist);
+        };
+        // (EXP: outputs meaningless, study builds only, make STUDY=1; Monaghan, M_TAIT)
+        if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
+          select_int<0, 1, 2, 3>(exp1, launch);
+        else
+          launch(std::integral_constant<int, 0>{});
+      });
+    });
+  });
 }
 
 }  // namespace sph

@@ -470,15 +470,38 @@ inline int sph_engine::build_blk_shape(int shape, bool big) {
     }
     // the inner rows over their own union
     const bool iu = v2 && want_inner;
-    if (v2)
-      blk_build(shape, nt1(), want_inner, s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p, qbeg.p,
-                dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p, ccnt.p, snbr.p, icnt.p, snbi.p,
-                mx.p, mx.p + 1, blk_cq(), study_int("SPH_BEXP", 0) | (blk_ksmall ? 0x100 : 0),
-                iu ? uilist.p : nullptr, iu ? uicnt.p : nullptr, kcnt.p);
-    else
-      blk_neigh(shape, big, nt1(), s, n, qb, cfg.dim, xf.p, ty.p, xb.p, tb.p, qbeg.p, xpos.p,
-                dc, BLK_UCAP, blk_sstride, ulist.p, ucnt.p, ccnt.p, snbr.p, mx.p, mx.p + 1,
-                blk_cq(), study_int("SPH_BEXP", 0));
+    BlkBuildArgs a;
+    a.n = n;
+    a.q = qb;
+    a.dim = cfg.dim;
+    a.xf = xf.p;
+    a.ty = ty.p;
+    a.xb = xb.p;
+    a.tb = tb.p;
+    a.qbeg = qbeg.p;
+    a.cf = dc;
+    a.ucap = BLK_UCAP;
+    a.sstride = blk_sstride;
+    a.ulist = ulist.p;
+    a.ucnt = ucnt.p;
+    a.rcnt = ccnt.p;
+    a.snbr = snbr.p;
+    a.ovf = mx.p;
+    a.umax = mx.p + 1;
+    a.cq = blk_cq();
+    a.bexp = study_int("SPH_BEXP", 0);
+    if (v2) {
+      a.icnt = icnt.p;
+      a.snbi = snbi.p;
+      a.uilist = iu ? uilist.p : nullptr;
+      a.uicnt = iu ? uicnt.p : nullptr;
+      a.kcnt = kcnt.p;
+      a.small = blk_ksmall;
+      blk_build(shape, nt1(), want_inner, s, a);
+    } else {
+      a.xpos = xpos.p;
+      blk_neigh(shape, big, nt1(), s, a);
+    }
     inner_written = v2 && want_inner;
     // the build's statistics: ONE read-back
     int *const hm = h_small;

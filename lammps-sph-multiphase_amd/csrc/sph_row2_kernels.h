@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sph_kernels.h"
+#include "sph_select.h"
 
 namespace sph {
 
@@ -434,82 +435,6 @@ inline bool row2_fits(long nall, long ntot) {
   return ntot * 4L < 0x7fffffffL && nall * 32L < 0x7fffffffL;
 }
 
-template <int G, int U, bool LP, bool IV>
-inline void row2_rhosum_k(bool nt1, hipStream_t s, const Row2Args &b) {
-  const RowArgs &a = b.a;
-  const int grid = (int)(((long long)a.n * G + 255) / 256);
-  if (grid == 0) return;
-  if (nt1)
-    hipLaunchKernelGGL((k_row2_rhosum<G, U, true, LP, IV>), dim3(grid), dim3(256), 0, s, a.n,
-                       b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr, a.cf,
-                       b.rows, b.tbits ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_row2_rhosum<G, U, false, LP, IV>), dim3(grid), dim3(256), 0, s, a.n,
-                       b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr, a.cf,
-                       b.rows, b.tbits ? 1 : 0);
-}
-
-template <int G, int U>
-inline void row2_rhosum_gu(bool nt1, hipStream_t s, const Row2Args &b) {
-  const bool iv = b.iv && U == 4;
-  if (b.lp) {
-    if (iv) row2_rhosum_k<G, U, true, U == 4>(nt1, s, b);
-    else row2_rhosum_k<G, U, true, false>(nt1, s, b);
-  } else {
-    if (iv) row2_rhosum_k<G, U, false, U == 4>(nt1, s, b);
-    else row2_rhosum_k<G, U, false, false>(nt1, s, b);
-  }
-}
-
-template <int G, int U, int VISC, int MODE, bool NT1, bool LP, bool IV, int EXP>
-inline void row2_force_t(hipStream_t s, const Row2Args &b) {
-  const RowArgs &a = b.a;
-  const int grid = (int)(((long long)a.n * G + 255) / 256);
-  if (grid == 0) return;
-  hipLaunchKernelGGL((k_row2_force<G, U, VISC, MODE, NT1, LP, IV, EXP>), dim3(grid), dim3(256),
-                     0, s, a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.vr,
-                     a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy, a.gz, b.rows, b.tbits ? 1 : 0);
-}
-
-template <int G, int U, bool NT1, bool LP, bool IV>
-inline void row2_force_n(int visc, int mode, hipStream_t s, const Row2Args &b) {
-  const bool mor = visc == SPH_VISC_MORRIS;
-  switch (mode) {
-    case M_TAIT:
-      if (mor) row2_force_t<G, U, 1, M_TAIT, NT1, LP, IV, 0>(s, b);
-#ifdef SPH_STUDY  // (outputs meaningless: study builds only, make STUDY=1)
-      else if (NT1 && b.exp == 1) row2_force_t<G, U, 0, M_TAIT, NT1, LP, IV, 1>(s, b);
-      else if (NT1 && b.exp == 2) row2_force_t<G, U, 0, M_TAIT, NT1, LP, IV, 2>(s, b);
-#endif
-      else row2_force_t<G, U, 0, M_TAIT, NT1, LP, IV, 0>(s, b);
-      break;
-    case M_TAIT | M_HEAT:
-      if (mor) row2_force_t<G, U, 1, M_TAIT | M_HEAT, NT1, LP, IV, 0>(s, b);
-      else row2_force_t<G, U, 0, M_TAIT | M_HEAT, NT1, LP, IV, 0>(s, b);
-      break;
-    case M_GAS: row2_force_t<G, U, 0, M_GAS, NT1, LP, IV, 0>(s, b); break;
-    default: row2_force_t<G, U, 0, M_HEAT, NT1, LP, IV, 0>(s, b); break;
-  }
-}
-
-template <int G, int U, bool LP, bool IV>
-inline void row2_force_l(bool nt1, int visc, int mode, hipStream_t s, const Row2Args &b) {
-  if (nt1) row2_force_n<G, U, true, LP, IV>(visc, mode, s, b);
-  else row2_force_n<G, U, false, LP, IV>(visc, mode, s, b);
-}
-
-template <int G, int U>
-inline void row2_force_gu(bool nt1, int visc, int mode, hipStream_t s, const Row2Args &b) {
-  const bool iv = b.iv && U == 4;
-  if (b.lp) {
-    if (iv) row2_force_l<G, U, true, U == 4>(nt1, visc, mode, s, b);
-    else row2_force_l<G, U, true, false>(nt1, visc, mode, s, b);
-  } else {
-    if (iv) row2_force_l<G, U, false, U == 4>(nt1, visc, mode, s, b);
-    else row2_force_l<G, U, false, false>(nt1, visc, mode, s, b);
-  }
-}
-
 // (G lanes per row, U pairs per lane) shapes; SPH_ROW2TILE picks one in study builds
 // (tuning); the production build has the measured fastest, 8 x 4
 #ifdef SPH_STUDY
@@ -520,36 +445,77 @@ inline void row2_force_gu(bool nt1, int visc, int mode, hipStream_t s, const Row
 
 int row2_tile();
 
+// f(Dims<G, U>{}) of the selected shape (sph_select.h); a value outside the table: 8 x 4
+SPH_SHAPE_SELECT(row2_tile_listed, SPH_ROW2_TILES)
+template <class F>
+inline void row2_select_tile(F &&f) {
+  if (!row2_tile_listed(row2_tile(), f)) f(Dims<8, 4>{});
+}
+
 // lanes per row of the selected shape when it can walk a chunk-transposed list (U = 4),
 // else 0
 inline int row2_iv_g() {
-  switch (row2_tile()) {
-#define SPH_CASE(k, G, U) \
-  case k: return U == 4 ? G : 0;
-    SPH_ROW2_TILES(SPH_CASE)
-#undef SPH_CASE
-    default: return 8;
-  }
+  int g = 0;
+  row2_select_tile([&](auto tile) { g = tile.v[1] == 4 ? tile.v[0] : 0; });
+  return g;
+}
+
+// f(Dims<G, U>{}, LP, IV, NT1): the selectors the two passes share; index vectors exist
+// only for U = 4
+template <class F>
+inline void row2_select(bool nt1, const Row2Args &b, F &&f) {
+  row2_select_tile([&](auto tile) {
+    constexpr int U = tile.v[1];
+    select_bool(b.lp, [&](auto lp) {
+      select_bool(b.iv, [&](auto iv) {
+        constexpr bool IV = iv && U == 4;
+        select_bool(nt1, [&](auto t) { f(tile, lp, std::bool_constant<IV>{}, t); });
+      });
+    });
+  });
 }
 
 inline void row2_rhosum(bool nt1, hipStream_t s, const Row2Args &b) {
-  switch (row2_tile()) {
-#define SPH_CASE(k, G, U) \
-  case k: row2_rhosum_gu<G, U>(nt1, s, b); break;
-    SPH_ROW2_TILES(SPH_CASE)
-#undef SPH_CASE
-    default: row2_rhosum_gu<8, 4>(nt1, s, b); break;
-  }
+  row2_select(nt1, b, [&](auto tile, auto lp, auto iv, auto t) {
+    constexpr int G = tile.v[0], U = tile.v[1];
+    constexpr bool LP = lp, IV = iv, NT1 = t;
+    const RowArgs &a = b.a;
+    const int grid = (int)(((long long)a.n * G + 255) / 256);
+    if (grid == 0) return;
+    hipLaunchKernelGGL((k_row2_rhosum<G, U, NT1, LP, IV>), dim3(grid), dim3(256), 0, s, a.n,
+                       b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr, a.xf, a.ty, a.vr, a.cf,
+                       b.rows, b.tbits ? 1 : 0);
+  });
 }
 
 inline void row2_force(bool nt1, int visc, int mode, hipStream_t s, const Row2Args &b) {
-  switch (row2_tile()) {
-#define SPH_CASE(k, G, U) \
-  case k: row2_force_gu<G, U>(nt1, visc, mode, s, b); break;
-    SPH_ROW2_TILES(SPH_CASE)
-#undef SPH_CASE
-    default: row2_force_gu<8, 4>(nt1, visc, mode, s, b); break;
-  }
+  const int exp1 = nt1 ? b.exp : 0;  // the study variants are for one type
+  row2_select(nt1, b, [&](auto tile, auto lp, auto iv, auto t) {
+    constexpr int G = tile.v[0], U = tile.v[1];
+    constexpr bool LP = lp, IV = iv, NT1 = t;
+    select_int<M_HEAT, M_TAIT, M_TAIT | M_HEAT, M_GAS>(mode, [&](auto m) {
+      constexpr int MODE = m;
+      select_bool(visc == SPH_VISC_MORRIS, [&](auto mor) {
+        // Morris viscosity exists only for the modes with M_TAIT
+        constexpr int VISC = (mor && (MODE & M_TAIT)) ? SPH_VISC_MORRIS : SPH_VISC_MONAGHAN;
+        auto launch = [&](auto ex) {
+          constexpr int EXP = ex;
+          const RowArgs &a = b.a;
+          const int grid = (int)(((long long)a.n * G + 255) / 256);
+          if (grid == 0) return;
+          hipLaunchKernelGGL((k_row2_force<G, U, VISC, MODE, NT1, LP, IV, EXP>), dim3(grid),
+                             dim3(256), 0, s, a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr,
+                             a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy, a.gz, b.rows,
+                             b.tbits ? 1 : 0);
+        };
+        // (EXP: outputs meaningless, study builds only, make STUDY=1; Monaghan, M_TAIT)
+        if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
+          select_int<0, 1, 2>(exp1, launch);
+        else
+          launch(std::integral_constant<int, 0>{});
+      });
+    });
+  });
 }
 
 }  // namespace sph

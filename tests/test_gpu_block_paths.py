@@ -2,12 +2,13 @@
 of them is a jittered lattice at h = 3, skin 0.3: rows of 147-163 entries in a 256-entry
 stride, unions inside the LDS image, constant density):
 
-A. the force pass's windowed walk (blk_force_body, nwin > 1) per physics of blk_force_n,
+A. the force pass's windowed walk (blk_force_body, nwin > 1) per physics of blk_force,
    through a rebuild, with the inner rows live;
 B. rows past the register preload (BlkArgs::pre() false: the NCH = 0 instantiations);
 C. the rebuild's retries (a row outgrows the slot-row stride, a block the small candidate
    image, both in one build) under a compression that grows the rows by ~1.6x;
-D. degenerate blocks: n < R, a last block with one live row, a row without neighbours.
+D. degenerate blocks: n < R, a last block with one live row, a row without neighbours;
+E. a build without inner rows (skin = 0).
 
 The reference is always pyoracle.RefRun(spread=True); the bars are test_gpu_engine's: counts
 bit-exact per particle, rho f drho de x v e at 1e-10 normwise + conftest.check_fields'
@@ -364,6 +365,29 @@ def test_retry_ladder_under_compression(gpu, sph_amd, case):
         assert seen & getattr(eng, "STAT_BLK_" + n), flag_names(eng, seen)
     if together:  # (the per-cause budget: one build that repeats for both causes and stays)
         assert both > 0, "no build repeated for " + " and ".join(together)
+
+
+# ---- E: a build without inner rows ------------------------------------------------------
+def test_zero_skin_builds_no_inner_rows(gpu, sph_amd):
+    """E. skin = 0 (a rebuild every step): the inner rows' margin, a sixteenth of the skin, is
+    zero, so k_blk_build runs its instantiation without the inner ballot and the passes walk
+    the full rows -- every other engine test has a skin and with it inner rows."""
+    s = c2_system(10)
+    ph = po.c2_physics()
+    ph.skin, ph.every = 0.0, 1
+    snaps, _ = oracle_snaps(s, ph, (1, 3))
+    assert np.abs(snaps[3].field("f")).max() > 0
+    eng = engine_for(sph_amd, s, ph)
+    eng.setup()
+    for k, steps in ((0, 0), (1, 1), (3, 2)):
+        if steps:
+            eng.run(steps)
+        st = eng.stats()
+        report(f"E skin 0 step {k}", eng, st)
+        assert st["step"] == k and st["staged"] == 1
+        assert st["inner_rows"] == 0 and st["inner_live"] == 0 and st["inner_refresh"] == 0
+        check_step(eng, snaps[k])
+    assert st["nbr_builds"] >= 4
 
 
 # ---- D: degenerate blocks ---------------------------------------------------------------
