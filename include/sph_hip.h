@@ -681,6 +681,54 @@ typedef struct {
 } sph_profile;
 int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, double *sum);
 
+/* Group centre of mass, momentum, bounds, volume and gyration on the device: the diagnostic
+   lines of the multiphase examples (bubble.lmp's xcm / vcm / bound(droplet,ymin) /
+   `compute dvol droplet reduce sum v_volume` with volume = mass/c_rho / count(droplet);
+   `compute rg droplet gyration` of the droplet scripts) without a get_atoms round trip.
+   A group is a type mask (0 = all) plus an optional static region tested at the wrapped
+   position, as everywhere in the engine; `fix phase_change` gives created atoms the type
+   to_type, so a type mask follows `group droplet type d` through the run.
+   Both calls work on the owned atoms of this rank in the state sph_engine_get_atoms would
+   return, after setup, on single-phase and multiphase engines, both kernel paths, with sort
+   and bricks; up to SPH_MAX_MOMENTS selections are evaluated in one pass over the atoms.
+   Each rank returns its own partial sums: adding the ranks and dividing by the total mass are
+   the caller's (the reference's MPI_Allreduce and the lines after it).
+   Arithmetic, every operation rounded on its own in the reference's order (no FMA):
+   unwrap[d] = x[d] + xbox[d] * prd[d] with the image counts xbox of the packed imageint
+   (Domain::unmap, domain.cpp:1307-1316, orthogonal box); then unwrap[d] * m (Group::xcm,
+   group.cpp:1002-1018), v[d] * m (Group::vcm, :1107-1125; v, not vest), m / rho, and for the
+   gyration dx = unwrap[0] - cm[0] ..., (dx*dx + dy*dy + dz*dz) * m (Group::gyration,
+   :1327-1336), dx*dx * m ... dy*dz * m (compute_gyration.cpp:92-108).  m = rmass on
+   multiphase engines, mass[type] otherwise.  lo / hi are the extremes of the stored
+   (wrapped) x (Group::bounds, :905-916).
+   Fixed-shape two-stage reductions without atomics: two calls on the same state return
+   identical bits.  An empty selection gives count 0, sums 0, lo = +inf, hi = -inf (the
+   reference's Group::bounds leaves +-BIG = +-1e20 there, a host convention).
+   SPH_HIP_EINVAL: a NULL argument with nsel > 0, nsel outside [0, SPH_MAX_MOMENTS], a
+   region_mode outside 0..2, an unknown region style, a negative radius, a call before setup.
+   nsel == 0 returns SPH_HIP_OK and touches nothing. */
+#define SPH_MAX_MOMENTS 8
+typedef struct {
+  int type_mask;       /* bit t: type t is in the group; 0 = all */
+  int region_mode;     /* 0 none, 1 `region` (where match), 2 where !match */
+  sph_region region;
+} sph_group_sel;
+typedef struct {
+  int64_t count;       /* atoms selected on this rank */
+  double mass;         /* Group::mass: sum m */
+  double mx[3];        /* Group::xcm's cmone: sum unwrap(x)[d] * m */
+  double mv[3];        /* Group::vcm's p: sum v[d] * m */
+  double lo[3], hi[3]; /* Group::bounds: min / max of the wrapped x */
+  double volume;       /* sum m / rho (compute reduce sum of mass/c_rho) */
+} sph_moments_out;
+int sph_engine_moments(sph_engine *e, int nsel, const sph_group_sel *sel, sph_moments_out *out);
+/* cm: nsel*3, the caller's (all-rank) centre of mass per selection.
+   out: nsel*7 = { sum m*(dx*dx+dy*dy+dz*dz), sum m*dx*dx, dy*dy, dz*dz, dx*dy, dx*dz, dy*dz }
+   about it: rg = sqrt(out[0] / masstotal), compute gyration's vector = out[1..6] / masstotal
+   (xx yy zz xy xz yz). */
+int sph_engine_gyration(sph_engine *e, int nsel, const sph_group_sel *sel, const double *cm,
+                        double *out);
+
 /* Multiphase fields of the owned atoms in get_atoms order (any pointer may be NULL):
    rmass, cv, colorgradient (n*3), vest (n*3), type; *ninserted = atoms created so far. */
 int sph_engine_get_atoms_multiphase(sph_engine *e, double *rmass, double *cv, double *cg,

@@ -122,6 +122,7 @@ SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7
 SPH_Q_VX, SPH_Q_VY, SPH_Q_VZ = 7, 8, 9
 SPH_MAX_SETMESO, SPH_MAX_REDUCE = 8, 16
 SPH_MAX_FORCEFIX, SPH_MAX_PROFILE_Q = 8, 8
+SPH_MAX_MOMENTS = 8
 SPH_FF_SET, SPH_FF_ADD = 0, 1
 SET_FIELDS = {"rho": SPH_SET_RHO, "e": SPH_SET_E, "t": SPH_SET_T, "de": SPH_SET_DE}
 QUANTITIES = {"one": SPH_Q_ONE, "rho": SPH_Q_RHO, "e": SPH_Q_E, "t": SPH_Q_T, "de": SPH_Q_DE,
@@ -175,6 +176,18 @@ class Profile(C.Structure):
                 ("nlayers", C.c_int), ("type_mask", C.c_int), ("region_mode", C.c_int),
                 ("region", Region), ("nq", C.c_int),
                 ("quantity", C.c_int * SPH_MAX_PROFILE_Q)]
+
+
+class GroupSel(C.Structure):
+    """sph_group_sel: a group (type mask) and an optional static region."""
+    _fields_ = [("type_mask", C.c_int), ("region_mode", C.c_int), ("region", Region)]
+
+
+class MomentsOut(C.Structure):
+    """sph_moments_out: one rank's partial sums of a selection."""
+    _fields_ = [("count", C.c_int64), ("mass", C.c_double), ("mx", C.c_double * 3),
+                ("mv", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+                ("volume", C.c_double)]
 
 
 def layers(origin, delta, boxlo, boxhi):
@@ -253,6 +266,8 @@ EXPORTS = {
     "sph_engine_forcefix": (_i, [_vp, C.POINTER(ForceFix), C.POINTER(_i)]),
     "sph_engine_forcefix_total": (_i, [_vp, _i, _dp]),
     "sph_engine_profile": (_i, [_vp, C.POINTER(Profile), _lp, _vp]),
+    "sph_engine_moments": (_i, [_vp, _i, _vp, _vp]),
+    "sph_engine_gyration": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sph_engine_idealgas": (_i, [_vp, C.POINTER(EngineGas)]),
     "sph_hip_idealgas_coeff": (_i, [_vp, _dp, _dp, _dp]),
     "sph_hip_idealgas": (_i, [_vp, _dp, _dp, _dp, _vp]),
@@ -883,6 +898,53 @@ class Engine:
         _chk(self.L.sph_engine_profile(self.h, C.byref(p), count, sums.ctypes.data))
         return count, sums[:p.nq]
 
+    @staticmethod
+    def _group_sels(selections):
+        n = len(selections)
+        sel = (GroupSel * max(n, 1))()
+        for k, d in enumerate(selections[:SPH_MAX_MOMENTS]):
+            sel[k].type_mask = _type_mask(d.get("types"))
+            sel[k].region_mode, sel[k].region = _region_mode(d.get("region"), d.get("noregion"))
+        return n, sel
+
+    def moments(self, selections):
+        """sph_engine_moments: selections = dicts(types=None, region=None, noregion=None), at
+        most SPH_MAX_MOMENTS, evaluated in one pass over this rank's owned atoms ->
+        [dict(count, mass, mx (3,), mv (3,), lo (3,), hi (3,), volume, xcm, vcm)].  mx sums
+        the unwrapped positions times m, mv sums v * m, lo / hi bound the wrapped positions,
+        volume sums m / rho.  xcm = mx / mass and vcm = mv / mass (zeros for mass 0, as
+        Group::xcm leaves them) are the group's only where this rank holds all of it; with
+        bricks, fold the ranks' results with combine_moments first."""
+        n, sel = self._group_sels(selections)
+        out = (MomentsOut * max(n, 1))()
+        _chk(self.L.sph_engine_moments(self.h, n, C.cast(sel, C.c_void_p),
+                                       C.cast(out, C.c_void_p)))
+        return [_moments_dict(int(o.count), o.mass, np.array(o.mx), np.array(o.mv),
+                              np.array(o.lo), np.array(o.hi), o.volume) for o in out[:n]]
+
+    def gyration(self, selections, cm=None, mass=None):
+        """sph_engine_gyration (compute gyration) -> [dict(rg, tensor (6,): xx yy zz xy xz yz,
+        sums (7,): this rank's raw sums)].  cm (nsel, 3) and mass (nsel,) are the groups'
+        centre of mass and total mass over all ranks; None takes this rank's own moments(),
+        which holds for one brick only -- a brick of a decomposition raises without them (add
+        the ranks' sums, then divide by the total mass)."""
+        n, sel = self._group_sels(selections)
+        if cm is None or mass is None:
+            if self.cfg.procgrid[0] * self.cfg.procgrid[1] * self.cfg.procgrid[2] > 1:
+                raise ValueError("gyration on one brick of a decomposition needs the groups' "
+                                 "cm and mass over all ranks (combine_moments)")
+            mom = self.moments(selections)
+            cm = [m["xcm"] for m in mom]
+            mass = [m["mass"] for m in mom]
+        cm = np.ascontiguousarray(cm, dtype=np.float64).reshape(-1, 3)
+        mass = np.ascontiguousarray(mass, dtype=np.float64).reshape(-1)
+        if cm.shape[0] != n or mass.shape[0] != n:
+            raise ValueError("gyration: one cm and one mass per selection")
+        sums = np.zeros((max(n, 1), 7))
+        _chk(self.L.sph_engine_gyration(self.h, n, C.cast(sel, C.c_void_p),
+                                        cm.ctypes.data if n else None, sums.ctypes.data))
+        return [gyration_dict(sums[k], mass[k]) for k in range(n)]
+
     def get_atoms_multiphase(self):
         n = self.nlocal
         out = dict(rmass=np.zeros(n), cv=np.zeros(n), cg=np.zeros((n, 3)), vest=np.zeros((n, 3)),
@@ -1025,6 +1087,41 @@ class Engine:
         s = EngineStats()
         _chk(self.L.sph_engine_stats_get(self.h, C.byref(s)))
         return s.as_dict()
+
+
+# ------------------------------------------------------------------------------------------
+# group moments on the host: the lines after the reference's MPI_Allreduce
+# ------------------------------------------------------------------------------------------
+def _moments_dict(count, mass, mx, mv, lo, hi, volume):
+    """xcm / vcm = the sums over the mass where it is positive (group.cpp:1022-1026)"""
+    d = dict(count=count, mass=mass, mx=mx, mv=mv, lo=lo, hi=hi, volume=volume)
+    d["xcm"] = mx / mass if mass > 0.0 else np.zeros(3)
+    d["vcm"] = mv / mass if mass > 0.0 else np.zeros(3)
+    return d
+
+
+def combine_moments(ranks):
+    """One selection's Engine.moments() results of every rank, folded in rank order (the
+    reference's MPI_Allreduce): sums and counts added, lo / hi by min / max."""
+    first = ranks[0]
+    acc = {k: (first[k].copy() if isinstance(first[k], np.ndarray) else first[k])
+           for k in ("count", "mass", "mx", "mv", "lo", "hi", "volume")}
+    for r in ranks[1:]:
+        for k in ("count", "mass", "mx", "mv", "volume"):
+            acc[k] = acc[k] + r[k]
+        acc["lo"] = np.minimum(acc["lo"], r["lo"])
+        acc["hi"] = np.maximum(acc["hi"], r["hi"])
+    return _moments_dict(**acc)
+
+
+def gyration_dict(sums, mass):
+    """rg = sqrt(sums[0] / mass) (Group::gyration; 0 for mass 0) and compute gyration's vector
+    sums[1:7] / mass (left as the sums for mass 0, compute_gyration.cpp:111) from the seven
+    sums of sph_engine_gyration, added over the ranks"""
+    sums = np.array(sums, dtype=np.float64)
+    if mass > 0.0:
+        return dict(rg=float(np.sqrt(sums[0] / mass)), tensor=sums[1:] / mass, sums=sums)
+    return dict(rg=0.0, tensor=sums[1:].copy(), sums=sums)
 
 
 # ------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #include "sph_engine_mp.h"
 #include "sph_fix_kernels.h"
 #include "sph_ipc.h"
+#include "sph_moments_kernels.h"
 #include "sph_mp2_kernels.h"
 #include "sph_pc.h"
 #include "sph_row2_kernels.h"
@@ -242,6 +243,7 @@ int sph_engine_destroy(sph_engine *e) {
   e->pf_idx2.release();
   e->pf_cnt.release();
   e->pf_sum.release();
+  e->mom_buf.release();
   for (auto *b : {&e->ty, &e->ty2, &e->tag, &e->tag2, &e->gowner, &e->gimg, &e->sel, &e->nsel,
                   &e->bidx, &e->bidx2, &e->cnt, &e->off, &e->nbr, &e->mx,
                   &e->ccnt, &e->qbeg, &e->tb, &e->xpos, &e->sel2, &e->rows_in, &e->rows_bd,
@@ -604,6 +606,87 @@ int sph_engine_profile(sph_engine *e, const sph_profile *p, int64_t *count, doub
   if (p->nq)
     e->to_host(sum, e->pf_sum.p, (size_t)p->nq * nl);
   SPH_HIP_TRY(hipStreamSynchronize(s));
+  SPH_API_END
+}
+
+// the checks sph_engine_moments and sph_engine_gyration share; -> the selections as given
+static void check_group_sels(const char *who, sph_engine *e, int nsel, const sph_group_sel *sel,
+                             const void *in, const void *out, sph_group_sel *to) {
+  SPH_REQUIRE(e, SPH_HIP_EINVAL, "%s: NULL engine", who);
+  SPH_REQUIRE(nsel >= 0 && nsel <= SPH_MAX_MOMENTS, SPH_HIP_EINVAL,
+              "%s: %d selections outside [0,%d]", who, nsel, SPH_MAX_MOMENTS);
+  SPH_REQUIRE(nsel == 0 || (sel && in && out), SPH_HIP_EINVAL, "%s: NULL argument", who);
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "%s: call sph_engine_setup first", who);
+  for (int k = 0; k < nsel; k++) {
+    check_region(who, sel[k].region_mode, sel[k].region);
+    to[k] = sel[k];
+  }
+}
+
+int sph_engine_moments(sph_engine *e, int nsel, const sph_group_sel *sel, sph_moments_out *out) {
+  SPH_API_BEGIN
+  MomentsArgs a{};
+  check_group_sels("sph_engine_moments", e, nsel, sel, sel, out, a.sel);
+  if (nsel == 0) return SPH_HIP_OK;
+  a.nsel = nsel;
+  for (int d = 0; d < 3; d++) a.prd[d] = e->box.prd[d];
+  const int n = e->nlocal;
+  if (n == 0) {
+    for (int k = 0; k < nsel; k++) {
+      out[k] = sph_moments_out{};
+      for (int d = 0; d < 3; d++) {
+        out[k].lo[d] = HUGE_VAL;
+        out[k].hi[d] = -HUGE_VAL;
+      }
+    }
+    return SPH_HIP_OK;
+  }
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  const int nb = (int)std::min<long>(blocks(n), RED_MAXBLOCKS);
+  const size_t npart = (size_t)RED_MAXBLOCKS * SPH_MAX_MOMENTS * MOM_SLOTS;
+  e->mom_buf.reserve(npart + SPH_MAX_MOMENTS * MOM_SLOTS);
+  double *part = e->mom_buf.p, *res = e->mom_buf.p + npart;
+  const double *rm = e->mp ? (const double *)e->rm.p : nullptr;
+  // (up to four selections keep a smaller register file: more waves per SIMD)
+  auto stage1 = nsel <= 4 ? k_moments_part<4> : k_moments_part<SPH_MAX_MOMENTS>;
+  hipLaunchKernelGGL(stage1, dim3(nb), dim3(RED_THREADS), 0, e->s, n, a, e->xf.p, e->vr.p,
+                     e->ty.p, e->vel.p, rm, e->type_mass(), part);
+  hipLaunchKernelGGL(k_moments_final, dim3(1), dim3(SPH_MAX_MOMENTS * MOM_SLOTS), 0, e->s, nb,
+                     nsel, part, res);
+  SPH_HIP_TRY(hipGetLastError());
+  e->to_host((double *)out, res, (size_t)nsel * MOM_OUT);
+  SPH_HIP_TRY(hipStreamSynchronize(e->s));
+  SPH_API_END
+}
+
+int sph_engine_gyration(sph_engine *e, int nsel, const sph_group_sel *sel, const double *cm,
+                        double *out) {
+  SPH_API_BEGIN
+  GyrationArgs a{};
+  check_group_sels("sph_engine_gyration", e, nsel, sel, cm, out, a.sel);
+  if (nsel == 0) return SPH_HIP_OK;
+  a.nsel = nsel;
+  for (int d = 0; d < 3; d++) a.prd[d] = e->box.prd[d];
+  for (int k = 0; k < nsel; k++)
+    for (int d = 0; d < 3; d++) a.cm[k][d] = cm[3 * k + d];
+  const int n = e->nlocal;
+  if (n == 0) {
+    for (int k = 0; k < nsel * GYR_OUT; k++) out[k] = 0.0;
+    return SPH_HIP_OK;
+  }
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  const int nb = (int)std::min<long>(blocks(n), RED_MAXBLOCKS);
+  const size_t npart = (size_t)RED_MAXBLOCKS * SPH_MAX_MOMENTS * MOM_SLOTS;
+  e->mom_buf.reserve(npart + SPH_MAX_MOMENTS * MOM_SLOTS);
+  double *part = e->mom_buf.p, *res = e->mom_buf.p + npart;
+  hipLaunchKernelGGL(k_gyration_part, dim3(nb), dim3(RED_THREADS), 0, e->s, n, a, e->xf.p,
+                     e->ty.p, e->vel.p, e->mp ? (const double *)e->rm.p : nullptr,
+                     e->type_mass(), part);
+  hipLaunchKernelGGL(k_gyration_final, dim3(1), dim3(SPH_MAX_MOMENTS * GYR_SLOTS), 0, e->s, nb,
+                     nsel, part, res);
+  SPH_HIP_TRY(hipGetLastError());
+  e->to_host(out, res, (size_t)nsel * GYR_OUT);
+  SPH_HIP_TRY(hipStreamSynchronize(e->s));
   SPH_API_END
 }
 

@@ -180,6 +180,8 @@ struct sph_engine {
   DBuf<int> pf_idx, pf_idx2;
   DBuf<long long> pf_cnt;
   DBuf<double> pf_sum;
+  // sph_engine_moments / sph_engine_gyration: the blocks' partials, then the folded results
+  DBuf<double> mom_buf;
   bool pc_tags_agreed = false;  // bricks: tag_next agreed over the ranks (first call)
   std::vector<double> cv_by_tag;  // single-phase engines: the constant cv, for restarts
 
