@@ -4,7 +4,10 @@
 // rsq <= cutneighsq, j != i).  Layout as in sph_kernels.h (xf, vr, ty, en).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
+#include "sph_bins.h"
+#include "sph_dispatch.h"
 #include "sph_kernels.h"
 #include "sph_mp2_kernels.h"
 
@@ -706,12 +709,7 @@ static __global__ void k_forward_rho(int nghost, int nlocal, const int *__restri
 }
 
 // ---- binning ----------------------------------------------------------------------------
-struct Bins {
-  double lo[3];
-  double inv[3];
-  int nb[3];
-};
-
+// (Bins: sph_bins.h)
 __device__ __forceinline__ int bin_coord(double x, double lo, double inv, int nb) {
   int c = (int)floor((x - lo) * inv);
   return c < 0 ? 0 : (c >= nb ? nb - 1 : c);
@@ -829,11 +827,7 @@ static __global__ void k_permute(int n, const int *__restrict__ perm,
 // already exceeds it are skipped.  The trimming is conservative (slab distances shrunk
 // by a margin) -- membership itself is decided only by rsq <= cutneighsq[it][jt] in
 // fp64, exactly as Neighbor::full_bin (neigh_full.cpp:241-344).
-struct QBins {
-  double lo[3], inv[3], size[3];
-  int nb[3];
-  double cutmaxsq;
-};
+// (QBins: sph_bins.h)
 
 // (xpos, if given: the inverse, atom -> position in xb)
 // (tpack: .w = j | (type - 1) << 28 -- the multiphase engine's list entry itself, so its
@@ -1226,6 +1220,72 @@ k_row_ghost_flags(int n, int nlocal, const int *__restrict__ off, int stride,
     bd[i] = any ? 1 : 0;
     in[i] = any ? 0 : 1;
   }
+}
+
+// ---- host side of the list build, shared by the engine (bin_q, list_q) and the pair layer ----
+// Bin-ordered copy of the atoms [0, nall) over the nbins bins of b: radix sort by linear bin
+// key (key, idx -> key2, idx2), the bins' starts beg[0 .. nbins], and the copy xb, tb (xpos,
+// if given: atom -> position in xb; tpack: k_bin_copy).  tmp is the sort's scratch.
+inline void bin_copy_radix(hipStream_t s, DBuf<unsigned char> &tmp, int nall, int nbins,
+                           const Bins &b, const double4 *xf, const int *ty, unsigned *key,
+                           unsigned *key2, int *idx, int *idx2, int *beg, double4 *xb, int *tb,
+                           int *xpos, int tpack) {
+  const dim3 atoms((nall + 255) / 256), block(256);
+  hipLaunchKernelGGL(k_bin_keys, atoms, block, 0, s, nall, 0, b, xf, key, idx, 0, 3);
+  with_scratch(tmp, [&](void *t, size_t &bytes) {
+    return hipcub::DeviceRadixSort::SortPairs(t, bytes, key, key2, idx, idx2, nall, 0,
+                                              key_bits(nbins), s);
+  });
+  hipLaunchKernelGGL(k_lower_bound, dim3((nbins + 1 + 255) / 256), block, 0, s, nbins, nall, 0,
+                     key2, beg);
+  hipLaunchKernelGGL(k_bin_copy, atoms, block, 0, s, nall, idx2, xf, ty, xb, tb, xpos, tpack);
+}
+
+// the arguments of k_neigh3 in the kernel's order (host side; the grid is the rows' at 8 lanes)
+struct Neigh3Args {
+  int n = 0;  // owned rows
+  QBins q{};
+  int dim = 3;
+  const double4 *xf = nullptr;  // the rows' positions and types
+  const int *ty = nullptr;
+  const double4 *xb = nullptr;  // the binned copy, its types and the bins' starts
+  const int *tb = nullptr, *qbeg = nullptr;
+  const Coefs *cf = nullptr;
+  int *cnt = nullptr;        // row counts (count pass, strided fill)
+  const int *off = nullptr;  // CSR fill: the rows' offsets
+  int *nbr = nullptr;        // fill: the rows; stride > 0: fixed-stride, a longer one raises *ovf
+  int stride = 0, *ovf = nullptr, perm_g = 0, tbits = 0;  // (perm_g, tbits: see the kernel)
+  const MpCoefs *mc = nullptr;  // RHO: the fused rhosum's coefficients, rmass and sums
+  const double *rm = nullptr;
+  double *rho = nullptr;
+  const int *tg = nullptr;  // tags: the orientation of owned pairs for k_mp_gather
+};
+
+// k_neigh3<8, 4, FILL, NT1, RHO, TP>: count or fill pass, one type or several.  MP admits the
+// multiphase engine's variants, tp (types packed into xb.w) and rho (the fused rhosum: fill
+// passes over packed types only); a unit that passes MP = false holds the four plain kernels
+template <bool MP>
+inline void launch_neigh3(bool fill, bool nt1, bool tp, bool rho, hipStream_t s,
+                          const Neigh3Args &a) {
+  SPH_REQUIRE((MP || (!tp && !rho)) && (!rho || (fill && tp)), SPH_HIP_EINVAL,
+              "k_neigh3: no variant fill %d, packed types %d, rhosum %d", fill, tp, rho);
+  select_bool(fill, [&](auto f) {
+    constexpr bool FILL = f;
+    select_bool(nt1, [&](auto t) {
+      constexpr bool NT1 = t;
+      select_bool(tp, [&](auto p) {
+        constexpr bool TP = p;
+        select_bool(rho, [&](auto r) {
+          constexpr bool RHO = r;
+          if constexpr ((MP || (!TP && !RHO)) && (!RHO || (FILL && TP)))
+            hipLaunchKernelGGL((k_neigh3<8, 4, FILL, NT1, RHO, TP>), dim3(grid_for_rows(a.n, 8)),
+                               dim3(256), 0, s, a.n, a.q, a.dim, a.xf, a.ty, a.xb, a.tb, a.qbeg,
+                               a.cf, a.cnt, a.off, a.nbr, a.stride, a.ovf, a.perm_g, a.tbits,
+                               a.mc, a.rm, a.rho, a.tg);
+        });
+      });
+    });
+  });
 }
 
 }  // namespace sph

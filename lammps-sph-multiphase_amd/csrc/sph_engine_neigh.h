@@ -3,7 +3,7 @@
 // bin geometry, the binned copy, the full list (strided rows or CSR), the block build with its
 // inner rows and their refresh, and neigh_modify's every / delay / check bookkeeping.
 // Writes: the owned arrays' order (sort_owned swaps them with their twins), cutneighmax /
-// cutghost, bn / qb and the bin arrays, the cs_* words of the counting sorts, the list (cnt,
+// cutghost, bn / qb / qbn and the bin arrays, the cs_* words of the counting sorts, the list (cnt,
 // off, nbr, ccnt, nbr_*, strided, list_*), the block path's state (blk, blk_*, ulist, ucnt,
 // snbr, uilist, uicnt, snbi, icnt, moved, x0, inner*), xhold / nm_flag and the nm_* counters,
 // last_sort, last_build, rho_fused_step and ov_ready.
@@ -115,12 +115,7 @@ inline void sph_engine::sort_owned() {
   const int morton = hil ? cb + 1 : (mort ? 1 : 0);
   // key bits: dim (Hilbert) or 3 (Morton) x bits of the largest cell dimension, else
   // bits(nbins)
-  int kb = 1;
-  if (mort) {
-    kb = cb * (hil ? cfg.dim : 3);
-  } else {
-    while ((1u << kb) < (unsigned)nbins && kb < 32) kb++;
-  }
+  const int kb = mort ? cb * (hil ? cfg.dim : 3) : key_bits(nbins);
   // the permutation bidx2: the counting sort over the 2^kb keys (k_cs_*: the order within a
   // key by index, as the stable radix sort's), else the radix sort
   cs_flags &= ~SPH_STAT_CSORT_ROWS;
@@ -231,32 +226,21 @@ inline void sph_engine::setup_bins_geometry() {
   // bound) takes bins three times finer in x: ~19 % fewer candidates per row, C5 11.54 ->
   // 11.17 ms per step (profiles/r06/qbx/); the block build of C2 gained nothing measurable
   const int fx = mp ? 3 : 1;
+  double ext[3];
+  int nb[3];
   for (int k = 0; k < 3; k++) {
-    const double ext = bn.nb[k] > 0 && bn.inv[k] > 0.0 ? bn.nb[k] / bn.inv[k] : 0.0;
-    int nb = 1;
-    if (k < cfg.dim) {
-      nb = (int)(ext / (0.5 * cutneighmax / (k == 0 ? fx : 1)));
-      if (nb < 1) nb = 1;
-      if (nb > 8192) nb = 8192;
-    }
-    qb.lo[k] = bn.lo[k];
-    qb.nb[k] = nb;
-    qb.inv[k] = (k < cfg.dim) ? nb / ext : 0.0;
-    qb.size[k] = (k < cfg.dim) ? ext / nb : 1.0;
+    ext[k] = bn.nb[k] > 0 && bn.inv[k] > 0.0 ? bn.nb[k] / bn.inv[k] : 0.0;
+    nb[k] = 1;
+    if (k < cfg.dim)
+      nb[k] = std::max(1, std::min((int)(ext[k] / (0.5 * cutneighmax / (k == 0 ? fx : 1))), 8192));
   }
-  qb.cutmaxsq = cutneighmax * cutneighmax;
+  fill_qbins(qb, qbn, bn.lo, ext, nb, cfg.dim, cutneighmax * cutneighmax);
   nqbins = qb.nb[0] * qb.nb[1] * qb.nb[2];
 }
 
 // bin-ordered copy of all atoms over the half-size bins (xb, tb, qbeg)
 inline void sph_engine::bin_q() {
   const int nall = nlocal + nghost;
-  Bins b;
-  for (int k = 0; k < 3; k++) {
-    b.lo[k] = qb.lo[k];
-    b.inv[k] = qb.inv[k];
-    b.nb[k] = qb.nb[k];
-  }
   bkey.reserve(nall);
   bkey2.reserve(nall);
   bidx.reserve(nall);
@@ -270,9 +254,9 @@ inline void sph_engine::bin_q() {
   xpos.reserve(nall);
   // the counting sort over the nqbins keys: its scan is qbeg itself, and its last pass
   // writes the bin-ordered copy (k_cs_place<true>: k_bin_copy fused; SPH_TUNE_CSORT 2 keeps
-  // the two apart); else the radix sort, k_lower_bound and k_bin_copy
+  // the two apart); else the radix sort, k_lower_bound and k_bin_copy (bin_copy_radix)
   cs_flags &= ~SPH_STAT_CSORT_BINS;
-  if (cs_count(0, nall, nqbins, b, 0, 3, qbeg)) {
+  if (cs_count(0, nall, nqbins, qbn, 0, 3, qbeg)) {
     launch(k_cs_scatter, nall, nall, bkey.p, (const int *)bkey2.p, qbeg.p, bidx.p);
     if (csort == 2) {
       launch(k_cs_place<false>, nall, nall, bkey.p, qbeg.p, bidx.p, bidx2.p,
@@ -286,16 +270,8 @@ inline void sph_engine::bin_q() {
     cs_flags |= SPH_STAT_CSORT_BINS;
     return;
   }
-  launch(k_bin_keys, nall, nall, 0, b, xf.p, bkey.p, bidx.p, 0, 3);  // (linear keys: hdim unused)
-  int endbit = 1;
-  while ((1u << endbit) < (unsigned)nqbins && endbit < 32) endbit++;
-  cub([&](void *t, size_t &tb) {
-    return hipcub::DeviceRadixSort::SortPairs(t, tb, bkey.p, bkey2.p, bidx.p, bidx2.p, nall, 0,
-                                              endbit, s);
-  });
-  launch(k_lower_bound, nqbins + 1, nqbins, nall, 0, bkey2.p, qbeg.p);
-  xpos.reserve(nall);
-  launch(k_bin_copy, nall, nall, bidx2.p, xf.p, ty.p, xb.p, tb.p, xpos.p, mp ? 1 : 0);
+  bin_copy_radix(s, tmp, nall, nqbins, qbn, xf.p, ty.p, bkey.p, bkey2.p, bidx.p, bidx2.p, qbeg.p,
+                 xb.p, tb.p, xpos.p, mp ? 1 : 0);
 }
 // Global-index full list (k_neigh3, Neighbor::full_bin membership) of the owned rows at
 // positions xi (default: the current ones, as binned by bin_q): CSR (count pass, scan,
@@ -313,43 +289,28 @@ inline void sph_engine::list_q(bool csr, const double4 *xi) {
   rho_fused_step = rho ? step : -1;  // (every path below ends in a fill pass)
   ccnt.reserve(n + 1);
   off.reserve(n + 1);
-  constexpr int G = 8;
-  dim3 grid(grid_for_rows(n, G)), block(BLK);
   auto pass = [&](bool fill, int stride, int *dst = nullptr) {
     if (n == 0) return;
-    const bool t = nt1();
+    const bool frho = fill && rho;
+    // (mp: xb packs the types, k_bin_copy tpack)
+    Neigh3Args a{n, qb, cfg.dim, xi_src, ty.p, xb.p, tb.p, qbeg.p, dc};
+    a.cnt = (!fill || stride > 0) ? ccnt.p : nullptr;
+    a.off = (fill && stride == 0) ? off.p : nullptr;
+    a.nbr = fill ? (dst ? dst : nbr.p) : nullptr;
+    a.stride = stride;
+    a.ovf = mx.p;
+    a.perm_g = stride > 0 ? list_perm_g : 0;
+    a.tbits = mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0);
+    if (frho) {
+      a.mc = dm;
+      a.rm = rm.p;
+      a.rho = rho_tmp.p;
+    }
     // asymmetric multiphase styles (k_mp_gather): owned pairs take the half-list orientation
     // of the reference's local order, i.e. by tag (k_neigh3 tg); the symmetric gathers
     // never read an owned pair's orientation
-    const int *const tgp = (mp && !mp2_symmetric(hm)) ? tag.p : (const int *)nullptr;
-    int *const cnt_out = (!fill || stride > 0) ? ccnt.p : (int *)nullptr;
-    int *const rows = dst ? dst : nbr.p;
-#define SPH_NGHP(F, T, P)                                                                       \
-hipLaunchKernelGGL((k_neigh3<G, 4, F, T, false, P>), grid, block, 0, s, n, qb, cfg.dim,       \
-                   xi_src, ty.p,                                                             \
-                   xb.p, tb.p, qbeg.p, dc, cnt_out,                                          \
-                   (F && stride == 0) ? off.p : (const int *)nullptr,                        \
-                   F ? rows : (int *)nullptr, stride, mx.p, stride > 0 ? list_perm_g : 0,    \
-                   mp ? 2 : ((stride > 0 && list_tbits) ? 1 : 0), (const MpCoefs *)nullptr,  \
-                   (const double *)nullptr, (double *)nullptr, tgp)
-#define SPH_NGHR(T)                                                                             \
-hipLaunchKernelGGL((k_neigh3<G, 4, true, T, true, true>), grid, block, 0, s, n, qb, cfg.dim,  \
-                   xi_src,                                                                   \
-                   ty.p, xb.p, tb.p, qbeg.p, dc, cnt_out,                                    \
-                   stride == 0 ? off.p : (const int *)nullptr, rows, stride, mx.p, 0, 2,    \
-                   dm, rm.p, rho_tmp.p, tgp)
-    // (mp: xb packs the types, k_bin_copy tpack)
-#define SPH_NGH(F, T)                                                                           \
-do {                                                                                        \
-  if (mp) SPH_NGHP(F, T, true);                                                              \
-  else SPH_NGHP(F, T, false);                                                                \
-} while (0)
-    if (fill && rho) { if (t) SPH_NGHR(true); else SPH_NGHR(false); }
-    else if (fill) { if (t) SPH_NGH(true, true); else SPH_NGH(true, false); }
-    else { if (t) SPH_NGH(false, true); else SPH_NGH(false, false); }
-#undef SPH_NGH
-#undef SPH_NGHP
-#undef SPH_NGHR
+    if (mp && !mp2_symmetric(hm)) a.tg = tag.p;
+    launch_neigh3<true>(fill, nt1(), mp, frho, s, a);
   };
   mx.reserve(8);
   // single pass into fixed-stride rows when a previous build sized them and nothing

@@ -278,7 +278,8 @@ struct sph_engine {
   // bins
   Bins bn{};
   int nbins = 0;
-  QBins qb{};
+  QBins qb{};  // the list builders' half-size bins, and the same grid for the binned copy's keys
+  Bins qbn{};
   int nqbins = 0;
   DBuf<int> qbeg, tb, xpos;
   DBuf<double4> xb;
@@ -467,7 +468,7 @@ struct sph_engine {
   void post_force_forcefix();
   bool rhosum_due() const;
   void setup();
-  void integrate_dt(bool alone, bool chk);
+  void launch_integrate(bool first, bool chk);
   void run(int nsteps);
 };
 

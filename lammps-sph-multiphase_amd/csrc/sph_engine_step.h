@@ -142,21 +142,19 @@ inline void sph_engine::dt_end_of_step(bool with_final) {
   const unsigned nb = blocks(nlocal);
   dt_part.reserve_min1(nb);
   const double *m = rm.p;
-  if (nb) {
-    if (with_final)
-      hipLaunchKernelGGL(k_dt_scan<true>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr, dt_rec.p,
+  if (nb)
+    select_bool(with_final, [&](auto f) {
+      constexpr bool INT = f;
+      hipLaunchKernelGGL(k_dt_scan<INT>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr, dt_rec.p,
                          vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
-    else
-      hipLaunchKernelGGL(k_dt_scan<false>, dim3(nb), dim3(BLK), 0, s, nlocal, sc, dtr,
-                         dt_rec.p, vr.p, en.p, ty.p, vel.p, fo.p, de.p, m, dt_part.p);
-  }
-  if (!(multi() && tr)) {
-    hipLaunchKernelGGL(k_dt_fold<false>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
+    });
+  const bool bricks = multi() && tr;
+  select_bool(bricks, [&](auto b) {
+    constexpr bool BRICK = b;
+    hipLaunchKernelGGL(k_dt_fold<BRICK>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
                        (long long)step, dt_rec.p);
-    return;
-  }
-  hipLaunchKernelGGL(k_dt_fold<true>, dim3(1), dim3(BLK), 0, s, (int)nb, dt_part.p, dtr,
-                     (long long)step, dt_rec.p);
+  });
+  if (!bricks) return;
   to_host(h_dt, dt_rec.p, 1);
   SPH_HIP_TRY(hipStreamSynchronize(s));
   uint64_t bits;
@@ -422,25 +420,23 @@ inline void sph_engine::pair_compute_mp() {
   const bool g1 = mp2_gamma1(hm);
   mp_flags = (mp_flags & SPH_STAT_MP_RHO_LISTFILL) |
              (sel == 0 ? 0 : sym && g1 ? SPH_STAT_MP_W4 : sym ? SPH_STAT_MP_POW : SPH_STAT_MP_ROW);
-  switch (sel) {
-#define SPH_MPG(k, T, S, H)                                                                   \
-case k:                                                                                     \
-  if (sym && g1)                                                                            \
-    hipLaunchKernelGGL((k_mp2_gather_w4<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);      \
-  else if (sym)                                                                             \
-    hipLaunchKernelGGL((k_mp2_gather<8, T, S, H, true>), mp_rows(n), dim3(256), 0, s, h);   \
-  else hipLaunchKernelGGL((k_mp_gather<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);       \
-  break;
-    SPH_MPG(1, true, false, false)
-    SPH_MPG(2, false, true, false)
-    SPH_MPG(3, true, true, false)
-    SPH_MPG(4, false, false, true)
-    SPH_MPG(5, true, false, true)
-    SPH_MPG(6, false, true, true)
-    SPH_MPG(7, true, true, true)
-#undef SPH_MPG
-    default: break;
-  }
+  select_bool(mpc.tait_on, [&](auto ta) {
+    constexpr bool T = ta;
+    select_bool(mpc.st_on, [&](auto st) {
+      constexpr bool S = st;
+      select_bool(mpc.heat_on, [&](auto he) {
+        constexpr bool H = he;
+        if constexpr (T || S || H) {  // (no style enabled: no gather)
+          if (sym && g1)
+            hipLaunchKernelGGL((k_mp2_gather_w4<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);
+          else if (sym)
+            hipLaunchKernelGGL((k_mp2_gather<8, T, S, H, true>), mp_rows(n), dim3(256), 0, s, h);
+          else
+            hipLaunchKernelGGL((k_mp_gather<8, T, S, H>), mp_rows(n), dim3(256), 0, s, h);
+        }
+      });
+    });
+  });
 }
 
 // single-phase engines keep no per-atom cv on the device (atom_style meso's cv takes no
@@ -539,28 +535,31 @@ inline void sph_engine::setup() {
   setup_done = true;
 }
 
-// The step's integrate launch of an engine with fix dt/reset: the same kernels in their
-// instantiations that take {dtv, dtf} from the device record.  alone: the previous step's
-// final integrate has run already (the first step of a run, or the step after a reset step).
-inline void sph_engine::integrate_dt(bool alone, bool chk) {
+// The step's integrate launch: the initial integrate alone when `first` (the final integrate
+// before it has run: the first step of a run, with fix dt/reset also the step after a reset
+// step), else fused behind the previous step's final one.  CHK: an eligible step of a check-yes
+// engine; DTR: an engine with fix dt/reset takes {dtv, dtf} from the device record.
+inline void sph_engine::launch_integrate(bool first, bool chk) {
   Scope t(this, T_INT);
-  const DtFrom<true> dr{&dt_rec.p->dtv};
-  const dim3 g(blocks(nlocal)), b(BLK);
-  if (chk) {
-    const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
-    if (alone)
-      hipLaunchKernelGGL((k_initial_integrate<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
-                         en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
-    else
-      hipLaunchKernelGGL((k_final_initial<true, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
-                         en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<true, true>{nh, dr});
-  } else if (alone) {
-    hipLaunchKernelGGL((k_initial_integrate<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p,
-                       en.p, ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
-  } else {
-    hipLaunchKernelGGL((k_final_initial<false, true>), g, b, 0, s, nlocal, sc, xf.p, vr.p, en.p,
-                       ty.p, vel.p, fo.p, de.p, rm.p, StepOpt<false, true>{{}, dr});
-  }
+  select_bool(chk, [&](auto c) {
+    constexpr bool CHK = c;
+    select_bool(dtr_on, [&](auto d) {
+      constexpr bool DTR = d;
+      StepOpt<CHK, DTR> o{};
+      if constexpr (CHK) {
+        o.xhold = xhold.p;
+        o.trig2 = 0.25 * cfg.skin * cfg.skin;
+        o.flag = nm_flag.p;
+      }
+      if constexpr (DTR) o.rec = &dt_rec.p->dtv;
+      if (first)
+        launch((k_initial_integrate<CHK, DTR>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p,
+               fo.p, de.p, rm.p, o);
+      else
+        launch((k_final_initial<CHK, DTR>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p,
+               fo.p, de.p, rm.p, o);
+    });
+  });
 }
 
 // Verlet::run (verlet.cpp:222-308)
@@ -579,26 +578,7 @@ inline void sph_engine::run(int nsteps) {
     const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
     const bool elig = !pc_due && neigh_eligible(nm_ago + 1);
     const bool chk = elig && nm_check;
-    if (dtr_on) {
-      integrate_dt(k == 0 || final_done, chk);
-    } else {
-      Scope t(this, T_INT);
-      if (chk) {
-        const NeighHold<true> nh{xhold.p, 0.25 * cfg.skin * cfg.skin, nm_flag.p};
-        if (k == 0)
-          launch((k_initial_integrate<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
-                 vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
-        else
-          launch((k_final_initial<true, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
-                 vel.p, fo.p, de.p, rm.p, StepOpt<true, false>{nh});
-      } else if (k == 0) {
-        launch((k_initial_integrate<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p,
-               vel.p, fo.p, de.p, rm.p, StepOpt<false, false>{});
-      } else {
-        launch((k_final_initial<false, false>), nlocal, nlocal, sc, xf.p, vr.p, en.p, ty.p, vel.p,
-               fo.p, de.p, rm.p, StepOpt<false, false>{});
-      }
-    }
+    launch_integrate(dtr_on ? (k == 0 || final_done) : k == 0, chk);
     bool build = pc_due;
     if (!pc_due) {
       nm_ago++;

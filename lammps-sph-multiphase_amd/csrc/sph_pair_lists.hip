@@ -8,9 +8,11 @@
 // SPH_LIST_HALF, Neighbor::half_from_full_newton's half of it (neigh_derive.cpp:83-150) --
 // the lists LAMMPS would have built for the style, so every pair style runs on them exactly
 // as on an uploaded NeighList, without the host list copy and its PCIe upload per rebuild.
-// Binning and the row builder are the engine's (half-size bins, k_neigh3: count pass, scan,
-// fill pass); rows come out in bin order rather than LAMMPS' stencil order, which changes
-// only the summation order of the pair sums.
+// Binning and the row builder are the engine's, kernels and host code (sph_bins.h fill_qbins,
+// sph_engine_kernels.h bin_copy_radix and launch_neigh3: half-size bins, count pass, scan, fill
+// pass); this file chooses the bins over the staged atoms' bounding box.  Rows come out in bin
+// order rather than LAMMPS' stencil order, which changes only the summation order of the pair
+// sums.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -227,8 +229,6 @@ int sph_hip_build_list(sph_hip_ctx *c, int kind, int64_t key, const double *cutn
       lo[k] = std::min(lo[k], hb[6 * b + k]);
       hi[k] = std::max(hi[k], hb[6 * b + 3 + k]);
     }
-  QBins q{};
-  Bins bn{};
   double lk[3], ek[3];
   int nbk[3];
   for (int k = 0; k < 3; k++) {
@@ -246,16 +246,10 @@ int sph_hip_build_list(sph_hip_ctx *c, int kind, int64_t key, const double *cutn
     const int k = (nbk[0] >= nbk[1] && nbk[0] >= nbk[2]) ? 0 : (nbk[1] >= nbk[2] ? 1 : 2);
     nbk[k] = (nbk[k] + 1) / 2;
   }
-  const long long nq = bins_of();
-  for (int k = 0; k < 3; k++) {
-    const bool act = k < c->dim;
-    q.lo[k] = bn.lo[k] = lk[k];
-    q.nb[k] = bn.nb[k] = nbk[k];
-    q.inv[k] = bn.inv[k] = act ? nbk[k] / ek[k] : 0.0;
-    q.size[k] = act ? ek[k] / nbk[k] : 1.0;
-  }
-  q.cutmaxsq = cmaxsq;
-  const int nqbins = (int)nq;
+  const int nqbins = (int)bins_of();
+  QBins q{};
+  Bins bn{};
+  fill_qbins(q, bn, lk, ek, nbk, c->dim, cmaxsq);
   // bin-ordered copy of every staged atom (xb, tb, qbeg)
   c->bkey.reserve(nall);
   c->bkey2.reserve(nall);
@@ -264,41 +258,27 @@ int sph_hip_build_list(sph_hip_ctx *c, int kind, int64_t key, const double *cutn
   c->qbeg.reserve(nqbins + 1);
   c->xb.reserve(nall);
   c->tb.reserve(nall);
-  hipLaunchKernelGGL(k_bin_keys, dim3((nall + 255) / 256), dim3(256), 0, c->stream, nall, 0, bn,
-                     c->xf.p, c->bkey.p, c->bidx.p, 0, 3);
-  int endbit = 1;
-  while ((1u << endbit) < (unsigned)nqbins && endbit < 32) endbit++;
-  with_scratch(c->tmp, [&](void *tmp, size_t &tb) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, c->bkey.p, c->bkey2.p, c->bidx.p,
-                                              c->bidx2.p, nall, 0, endbit, c->stream);
-  });
-  hipLaunchKernelGGL(k_lower_bound, dim3((nqbins + 1 + 255) / 256), dim3(256), 0, c->stream,
-                     nqbins, nall, 0, c->bkey2.p, c->qbeg.p);
-  hipLaunchKernelGGL(k_bin_copy, dim3((nall + 255) / 256), dim3(256), 0, c->stream, nall,
-                     c->bidx2.p, c->xf.p, c->ty.p, c->xb.p, c->tb.p, (int *)nullptr, 0);
+  bin_copy_radix(c->stream, c->tmp, nall, nqbins, bn, c->xf.p, c->ty.p, c->bkey.p, c->bkey2.p,
+                 c->bidx.p, c->bidx2.p, c->qbeg.p, c->xb.p, c->tb.p, nullptr, 0);
   // the full list: count pass, scan, fill pass (k_neigh3: Neighbor::full_bin membership)
-  constexpr int G = 8;
   c->lcnt.reserve(nlocal + 1);
   c->lbad.reserve(1);
-  const dim3 grid(grid_for_rows(nlocal, G)), block(256);
   const bool nt1 = nt == 1;
   DBuf<int> &foff = c->loff, &fnbr = c->lnbr;
-#define SPH_NGHL(F, T, OFF, NBR)                                                                 \
-  hipLaunchKernelGGL((k_neigh3<G, 4, F, T>), grid, block, 0, c->stream, nlocal, q, c->dim,        \
-                     (const double4 *)c->xf.p, (const int *)c->ty.p, (const double4 *)c->xb.p,    \
-                     (const int *)c->tb.p, (const int *)c->qbeg.p, (const Coefs *)c->dc,         \
-                     (F ? (int *)nullptr : c->lcnt.p), OFF, NBR, 0, c->lbad.p, 0, 0)
-  if (nt1) SPH_NGHL(false, true, (const int *)nullptr, (int *)nullptr);
-  else SPH_NGHL(false, false, (const int *)nullptr, (int *)nullptr);
+  Neigh3Args a{nlocal, q, c->dim, c->xf.p, c->ty.p, c->xb.p, c->tb.p, c->qbeg.p, c->dc};
+  a.cnt = c->lcnt.p;
+  a.ovf = c->lbad.p;
+  launch_neigh3<false>(false, nt1, false, false, c->stream, a);
   const long long ftot = scan_counts(c, c->lcnt.p, nlocal, foff);
   SPH_REQUIRE(ftot >= 0 && ftot < 0x7fffffffll, SPH_HIP_EOVERFLOW,
               "sph_hip_build_list: %lld list entries", ftot);
   fnbr.reserve(ftot > 0 ? ftot : 1);
   if (ftot) {
-    if (nt1) SPH_NGHL(true, true, (const int *)foff.p, fnbr.p);
-    else SPH_NGHL(true, false, (const int *)foff.p, fnbr.p);
+    a.cnt = nullptr;
+    a.off = foff.p;
+    a.nbr = fnbr.p;
+    launch_neigh3<false>(true, nt1, false, false, c->stream, a);
   }
-#undef SPH_NGHL
   if (kind == SPH_LIST_FULL) {
     std::swap(c->off, foff);
     std::swap(c->nbr, fnbr);

@@ -310,6 +310,7 @@ CASES = {
     "shock": (_shock, dict(nevery=1, tmin=1e-3, tmax=0.1, xmax=2e-3), None, 20),
     "mp": (_mp, dict(nevery=1, tmin=1e-4, tmax=4e-3, xmax=2e-4), None, 20),
     "c2_check": (_c2_check, dict(nevery=1, tmin=1e-4, tmax=2e-3, xmax=2e-2), (1, 0, 1), 16),
+    "c2_check_every3": (_c2_check, dict(nevery=3, tmin=1e-4, tmax=2e-3, xmax=2e-2), (1, 0, 1), 16),
     "water": (_water, dict(nevery=1, tmin=None, tmax=3e-4, xmax=1e-5), (5, 0, 0), 20),
     "bricks": (_bricks, dict(nevery=1, tmin=1e-5, tmax=2e-3, xmax=6.3e-5), None, 12),
 }

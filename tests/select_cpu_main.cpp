@@ -1,9 +1,13 @@
-// Stand-alone check of csrc/sph_select.h (tests/test_select_cpu.py builds and runs it with a
-// host compiler): every helper hands its lambda the constant it was told to, a value outside
-// a list takes the declared fall-back, and nested helpers compose.
+// Stand-alone check of csrc/sph_select.h and csrc/sph_bins.h (tests/test_select_cpu.py builds
+// and runs it with a host compiler): every helper hands its lambda the constant it was told to,
+// a value outside a list takes the declared fall-back, and nested helpers compose; with
+// arguments it prints the bin geometry fill_qbins computes from them.
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
+#include "sph_bins.h"
 #include "sph_select.h"
 
 static int g_fail = 0;
@@ -36,8 +40,34 @@ static void pick(int v, int *got, int *calls) {
   });
 }
 
-int main() {
+// `bins dim cutmaxsq lo0 ext0 nb0 lo1 ext1 nb1 lo2 ext2 nb2`: the fields fill_qbins leaves in
+// its QBins and Bins, doubles as hexadecimal floats (every bit)
+static int print_bins(char **v) {
+  double lo[3], ext[3];
+  int nb[3];
+  for (int k = 0; k < 3; k++) {
+    lo[k] = std::strtod(v[2 + 3 * k], nullptr);
+    ext[k] = std::strtod(v[3 + 3 * k], nullptr);
+    nb[k] = std::atoi(v[4 + 3 * k]);
+  }
+  QBins q{};
+  Bins b{};
+  fill_qbins(q, b, lo, ext, nb, std::atoi(v[0]), std::strtod(v[1], nullptr));
+  for (int k = 0; k < 3; k++)
+    std::printf("axis %d q %a %a %a %d b %a %a %d\n", k, q.lo[k], q.inv[k], q.size[k], q.nb[k],
+                b.lo[k], b.inv[k], b.nb[k]);
+  std::printf("cutmaxsq %a\n", q.cutmaxsq);
+  return 0;
+}
+
+int main(int argc, char **argv) {
   static_assert(!STUDY_BUILD, "built without SPH_STUDY");
+  if (argc == 13 && std::strcmp(argv[1], "bins") == 0) return print_bins(argv + 2);
+
+  // key_bits: the radix sort's bits cover the keys [0, n), at least one and at most 31
+  CHECK(key_bits(1) == 1 && key_bits(2) == 1 && key_bits(3) == 2 && key_bits(4) == 2 &&
+        key_bits(5) == 3 && key_bits(1 << 26) == 26 && key_bits((1 << 26) + 1) == 27 &&
+        key_bits(0x7fffffff) == 31);
 
   // select_bool: true and false give their own constants, one call each
   for (int b = 0; b < 2; b++) {

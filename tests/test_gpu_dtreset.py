@@ -289,6 +289,21 @@ def test_with_neigh_check(gpu, sph_amd, path):
     eng.close()
 
 
+def test_with_neigh_check_between_resets(gpu, sph_amd):
+    """the same with a reset every 3 steps: the steps between two resets take the fused
+    final + initial integrate in its CHK and DTR form (k_final_initial<true, true>), which a
+    reset at every step never launches"""
+    eng, ref, dts = run_case(sph_amd, "c2_check_every3", single_engine)
+    ns = eng.neigh_stats()
+    print("c2_check_every3", ns, ref.build_steps)
+    assert ns == dict(builds=len(ref.build_steps), dangerous=ref.ndanger,
+                      checks=len(ref.eligible_steps), last_build=ref.build_steps[-1])
+    assert len(ref.build_steps) > 1 and len(ref.eligible_steps) == 16
+    finish_single(eng, ref, dts, "c2_check_every3", 0)
+    assert dts[0] == dts[1] == dts[2] != dts[3]
+    eng.close()
+
+
 # ---- 7. argument errors and calling time ----------------------------------------------------------
 def test_argument_errors_and_calling_time(gpu, sph_amd):
     cls, s, ph, kw, dtfix, nm, steps = case_inputs("c2")

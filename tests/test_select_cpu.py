@@ -1,9 +1,11 @@
 """csrc/sph_select.h, the helpers that turn the launchers' run-time selectors into template
-arguments, checked on the CPU: tests/select_cpu_main.cpp includes that header and nothing else
-of the project, is built with a host compiler under AddressSanitizer + UndefinedBehaviorSanitizer
-and run once.  It checks that each listed value reaches the lambda as its own constant, an
-unlisted one as the declared fall-back, true / false as theirs, and that nested helpers
-compose (bool x int x shape)."""
+arguments, and csrc/sph_bins.h, the bin geometry the engine and the pair layer share, checked on
+the CPU: tests/select_cpu_main.cpp includes those two headers and nothing else of the project, is
+built once with a host compiler under AddressSanitizer + UndefinedBehaviorSanitizer and run as a
+program of its own.  Without arguments it checks that each listed value reaches the lambda as
+its own constant, an unlisted one as the declared fall-back, true / false as theirs, and that
+nested helpers compose (bool x int x shape).  With a bin grid as arguments it prints what
+fill_qbins makes of it, which is compared bit for bit with the same expressions in float64."""
 import os
 import shutil
 import subprocess
@@ -21,18 +23,100 @@ def _cxx():
     return None
 
 
-@pytest.mark.skipif(_cxx() is None, reason="needs a host C++ compiler")
-def test_select_helpers(tmp_path):
-    exe = tmp_path / "select_check"
+pytestmark = pytest.mark.skipif(_cxx() is None, reason="needs a host C++ compiler")
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    path = tmp_path_factory.mktemp("select") / "select_check"
     b = subprocess.run([_cxx(), "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
                         "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", str(exe),
+                        "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-o", str(path),
                         os.path.join(ROOT, "tests", "select_cpu_main.cpp")],
                        capture_output=True, text=True, timeout=120)
     assert b.returncode == 0, b.stderr
+    return str(path)
+
+
+def _run(exe, *args):
     env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0:detect_leaks=1:abort_on_error=0",
                UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, env=env)
+    r = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=env)
     assert r.returncode == 0, r.stdout + r.stderr[-4000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
-    assert "select: all checks passed" in r.stdout
+    return r.stdout
+
+
+def test_select_helpers(exe):
+    assert "select: all checks passed" in _run(exe)
+
+
+def _clamp(v, lo, hi):
+    return max(lo, min(int(v), hi))
+
+
+def _engine_grid(sublo, subhi, dim, cut, fx):
+    """lo, ext, nb of the half-size bins as sph_engine::setup_bins_geometry chooses them: the
+    sub-box widened by the ghost cutoff, its extent as the coarse bins give it back, bins of
+    cut / 2 (cut / 2 / fx in x), at most 8192 per axis."""
+    lo, ext, nb = [], [], []
+    for k in range(3):
+        if k < dim:
+            l, e0 = sublo[k] - cut, (subhi[k] + cut) - (sublo[k] - cut)
+            nc = _clamp(e0 / cut, 1, 4096)
+            e = nc / (nc / e0)
+            n = _clamp(e / (0.5 * cut / (fx if k == 0 else 1)), 1, 8192)
+        else:
+            l, e, n = sublo[k], 0.0, 1
+        lo.append(l), ext.append(e), nb.append(n)
+    return lo, ext, nb
+
+
+def _pair_grid(blo, bhi, dim, cut):
+    """the same for the pair layer (sph_hip_build_list): the atoms' bounding box plus a pad"""
+    lo, ext, nb = [], [], []
+    for k in range(3):
+        pad = 1e-6 * max(1.0, bhi[k] - blo[k])
+        e = (bhi[k] - blo[k]) + 2 * pad
+        lo.append(blo[k] - pad), ext.append(e)
+        nb.append(_clamp(e / (0.5 * cut), 1, 8192) if k < dim else 1)
+    return lo, ext, nb
+
+
+CUT = 0.39
+GRIDS = {
+    "box3d": (3, _engine_grid((0.0, -1.5, 0.25), (10.0, 11.0, 7.55), 3, CUT, 1)),
+    "box2d": (2, _engine_grid((0.0, 0.0, -0.5), (6.3, 9.1, 0.5), 2, CUT, 1)),
+    "clamp8192": (3, _engine_grid((0.0, 0.0, 0.0), (5000.0, 4.0, 4.0), 3, CUT, 1)),
+    "one_bin": (3, _pair_grid((0.0, 2.0, 0.0), (8.0, 2.0, 5.0), 3, CUT)),
+    "multiphase_fx3": (3, _engine_grid((0.0, 0.0, 0.0), (1.0e-3, 1.0e-3, 0.7e-3), 3, 7.5e-5, 3)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(GRIDS))
+def test_bin_geometry(exe, name):
+    dim, (lo, ext, nb) = GRIDS[name]
+    if name == "clamp8192":
+        assert nb[0] == 8192
+    if name == "one_bin":
+        assert nb[1] == 1
+    if name == "multiphase_fx3":
+        assert nb[0] > 2 * nb[1]
+    cutmaxsq = CUT * CUT
+    args = ["bins", str(dim), cutmaxsq.hex()]
+    for k in range(3):
+        args += [lo[k].hex(), ext[k].hex(), str(nb[k])]
+    out = _run(exe, *args).split("\n")
+    for k in range(3):
+        act = k < dim
+        n = nb[k] if act else 1
+        inv = nb[k] / ext[k] if act else 0.0   # the two expressions, as the parent had them
+        size = ext[k] / nb[k] if act else 1.0
+        w = out[k].split()
+        assert w[:3] == ["axis", str(k), "q"] and w[7] == "b", out[k]
+        q = [float.fromhex(x).hex() for x in w[3:6]] + [int(w[6])]
+        b = [float.fromhex(x).hex() for x in w[8:10]] + [int(w[10])]
+        assert q == [lo[k].hex(), inv.hex(), size.hex(), n], (name, k, out[k])
+        assert b == [lo[k].hex(), inv.hex(), n], (name, k, out[k])
+    w = out[3].split()
+    assert w[0] == "cutmaxsq" and float.fromhex(w[1]).hex() == cutmaxsq.hex()
