@@ -380,6 +380,9 @@ typedef struct {
    the two bits on every path */
 #define SPH_STAT_CSORT_BINS (1 << 10)
 #define SPH_STAT_CSORT_ROWS (1 << 11)
+/* at least one step of the most recent sph_engine_run had its integrate done by the block
+   force pass (SPH_TUNE_FUSEINT) */
+#define SPH_STAT_FUSEINT (1 << 12)
 
 typedef struct sph_engine sph_engine;
 
@@ -417,10 +420,15 @@ int sph_engine_comm_ipc(sph_engine *e, const char *name, int nranks, int rank, i
    exchange (1) or not (0, default).  SPH_TUNE_BLKUMF: cap the block force pass's LDS image
    at `value` records, blocks with larger unions going to its second launch (0 = auto).
    SPH_TUNE_CSORT: the rebuild orders bins and rows by counting sorts (1, default) or by the
-   radix sorts alone (0); 2 = counting, the bin copy as a pass of its own (measurement). */
+   radix sorts alone (0); 2 = counting, the bin copy as a pass of its own (measurement).
+   SPH_TUNE_FUSEINT: the block force pass integrates each row in its epilogue (1, default) on
+   the steps that allow it -- one brick, taitwater alone, no post_force fix, fix dt/reset, fix
+   phase_change or check yes, not the last step of a run -- or every step launches the
+   integrate kernel (0). */
 #define SPH_TUNE_OVERLAP 1
 #define SPH_TUNE_BLKUMF 2
 #define SPH_TUNE_CSORT 3
+#define SPH_TUNE_FUSEINT 4
 int sph_engine_tune(sph_engine *e, int key, int value);
 /* SPH_STAT_CSORT_* of the last build, on every pair path */
 int sph_engine_csort_paths(sph_engine *e, int *mask);

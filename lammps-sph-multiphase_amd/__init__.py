@@ -1040,7 +1040,9 @@ class Engine:
         _chk(self.L.sph_engine_comm_init(self.h, buf, nranks, rank))
 
     # TUNE_CSORT: 1 = the rebuild's counting sorts (default), 0 = the radix sorts alone
-    TUNE_OVERLAP, TUNE_BLKUMF, TUNE_CSORT = 1, 2, 3
+    # TUNE_FUSEINT: 1 = the block force pass integrates each row in its epilogue on the steps
+    # that allow it (default), 0 = every step launches the integrate kernel
+    TUNE_OVERLAP, TUNE_BLKUMF, TUNE_CSORT, TUNE_FUSEINT = 1, 2, 3, 4
 
     def tune(self, key: int, value: int):
         """sph_engine_tune: a schedule choice that does not change results (before setup)."""
@@ -1077,6 +1079,8 @@ class Engine:
     # the last build's bin copy / the last row sort took the counting sort (in flags on the
     # block path and in multiphase engines; csort_paths() on every path)
     STAT_CSORT_BINS, STAT_CSORT_ROWS = 1 << 10, 1 << 11
+    # at least one step of the last run() was integrated by the block force pass (TUNE_FUSEINT)
+    STAT_FUSEINT = 1 << 12
 
     def csort_paths(self) -> int:
         m = _i(0)

@@ -1241,6 +1241,22 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
 // xf.w = 0.4 e/m/rho (k_eos_gas) and the viscosity term's c_i + c_j.  The neighbour's
 // c_j = sqrt(e_j * 0.4/m_j) is computed once per STAGED record and kept in the fifth field of
 // the 80-byte image (+1024, where the heat mode keeps e_j); the sentinel's is 0.
+// FUSE (taitwater alone, MODE == M_TAIT; the engine's one-brick step): the row-leader lane does
+// not store the row's force and de but integrates the row with them -- FixMeso's final integrate
+// of this step and the initial integrate of the next, k_final_initial's body
+// (final_initial_atom) -- and writes the next step's x and {vest, rho} into the OTHER xf / vr
+// pair (xn, vn: the pass still reads other rows' records of this step from xf and vr), v and e
+// in place.  The heat and gas modes stage their neighbours' e, which the epilogue would
+// overwrite under them: they would need e in two buffers as well and stay unfused.
+template <bool FUSE>
+struct BlkFuse {};
+template <>
+struct BlkFuse<true> {
+  StepConst sc;      // (x0, lim2 and moved: the inner rows' check of the NEXT step's positions)
+  double4 *xn, *vn;  // the other xf / vr pair
+  double4 *vel;
+  double *en;
+};
 #define SPH_BLK_FORCE_PARAMS                                                              \
   int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, int ucap,                 \
       const unsigned short *__restrict__ snbr, int sstride, const int *__restrict__ rcnt,     \
@@ -1250,13 +1266,15 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
       double gx, double gy, double gz, int um, int cq,                                        \
       const unsigned short *__restrict__ snbi, const int *__restrict__ icnt,                  \
       const int *__restrict__ moved, const int *__restrict__ uilist,                          \
-      const int *__restrict__ uicnt, const int *__restrict__ blist
+      const int *__restrict__ uicnt, const int *__restrict__ blist, BlkFuse<FUSE> fu
 #define SPH_BLK_FORCE_ARGS                                                                \
   n, ulist, ucnt, ucap, snbr, sstride, rcnt, xf, vr, ty, en, cf, fo, de, gx, gy, gz, um, cq, \
-      snbi, icnt, moved, uilist, uicnt, blist
+      snbi, icnt, moved, uilist, uicnt, blist, fu
 // (the body of the force pass; the kernels below differ only in their occupancy request)
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, int AHEAD = 1>
+template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, int AHEAD = 1,
+          bool FUSE = false>
 __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
+  static_assert(!FUSE || (MODE == M_TAIT && EXP == 0), "FUSE: taitwater alone");
   if (snbi && *moved == 0) {  // (workgroup-uniform) the inner rows are still exact
     snbr = snbi;
     rcnt = icnt;
@@ -1483,22 +1501,45 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   if (HEAT) EH = group_sum<G>(EH);
   if (lane == 0 && live) {
     double dE = 0.0;
+    double4 f = make_double4(0.0, 0.0, 0.0, 0.0);
     if (TAIT) {
       // one type: F, E scale by m_i m_j wK (mm = -m_i m_j), D by m_j wK
       const double g = NT1 ? t1.mm * t1.wK : 1.0;
       const double gd = NT1 ? t1.mj * t1.wK : 1.0;
       const double m = cf->mass[it];
-      fo[row] = make_double4(g * fx + m * gx, g * fy + m * gy, g * fz + m * gz, gd * D);
+      f = make_double4(g * fx + m * gx, g * fy + m * gy, g * fz + m * gz, gd * D);
       dE = -0.5 * (g * E);
     }
     if (HEAT) dE += NT1 ? (h1.hmD * h1.wK) * EH : EH;
-    de[row] = dE;
+    if constexpr (FUSE) {
+      // v, e and the inner rows' x0 are loaded here, behind the walk and the reductions, so
+      // that the walk's register budget is what it was: asked for ahead of the reductions
+      // they cost the six-wave instantiation 28 B of scratch per lane (FOLDV scaled the
+      // register's rho: the stored one)
+      const StepConst &sc = fu.sc;
+      const bool moving = !((sc.stationary_mask >> it) & 1);
+      double4 x = xi, vv = vi, v = make_double4(0.0, 0.0, 0.0, 0.0);
+      if (FOLDV) vv.w = vr[row].w;
+      double e = fu.en[row];
+      if (moving) v = fu.vel[row];
+      final_initial_atom(sc.dtv, sc.dtf, sc.mass[it], moving, f, dE, x, v, vv, e);
+      if (moving) {
+        fu.vel[row] = v;
+        inner_check(sc, row, x);
+      }
+      fu.xn[row] = x;  // (x.w = P/rho^2 rides along; a stationary row's record is copied)
+      fu.vn[row] = vv;
+      fu.en[row] = e;
+    } else {
+      if (TAIT) fo[row] = f;
+      de[row] = dE;
+    }
   }
 }
 
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
+template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false>
 __global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
-  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP>(SPH_BLK_FORCE_ARGS);
+  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 1, FUSE>(SPH_BLK_FORCE_ARGS);
 }
 // one type, taitwater alone (C2): asked for 6 waves per SIMD (<= 80 VGPRs: what the 49 KiB
 // image allows, three workgroups per CU) with no records read ahead -- the other waves cover
@@ -1507,10 +1548,10 @@ __global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
 // 0.2497 vs 0.2632 / 0.2627 ms against that (profiles/r05/README.md).  The heat and
 // multi-type variants keep the default (at 96 VGPRs they would spill), and so does the gas
 // mode (M_GAS: the heat-size image and one more operand per pair).
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0>
+template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false>
 __global__ void __launch_bounds__(R * G) __attribute__((amdgpu_waves_per_eu(6, 6)))
 k_blk_force_w6(SPH_BLK_FORCE_PARAMS) {
-  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 0>(SPH_BLK_FORCE_ARGS);
+  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 0, FUSE>(SPH_BLK_FORCE_ARGS);
 }
 
 // blocks of a build whose union exceeds the force pass's LDS image (um records): the pass
@@ -1775,9 +1816,12 @@ inline void blk_inner(bool nt1, hipStream_t s, const BlkArgs &k, const double4 *
   });
 }
 
+// fuse != nullptr: the pass integrates each row in its epilogue (BlkFuse; M_TAIT alone)
 inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs &k,
-                      const RowArgs &a) {
+                      const RowArgs &a, const BlkFuse<true> *fuse = nullptr) {
   if (k.n == 0) return;
+  SPH_REQUIRE(!fuse || (mode == M_TAIT && (!nt1 || k.exp == 0)), SPH_HIP_EINVAL,
+              "blk_force: the fused integrate exists for taitwater alone (mode %d)", mode);
   // BLK_VISC_NONE and the study variants are for one type
   const int visc1 = (visc == BLK_VISC_NONE && !nt1) ? SPH_VISC_MONAGHAN : visc;
   const int exp1 = nt1 ? k.exp : 0;
@@ -1791,14 +1835,17 @@ inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs
         // M_TAIT alone
         constexpr int VISC = (MODE == M_TAIT || (vc == SPH_VISC_MORRIS && (MODE & M_TAIT)))
                                  ? (int)vc : SPH_VISC_MONAGHAN;
-        auto launch = [&](auto ex) {
+        auto launch = [&](auto ex, auto fz) {
           constexpr int EXP = ex;
+          constexpr bool FUSE = decltype(fz)::value && MODE == M_TAIT && EXP == 0;
           auto fn = [] {
             if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0)
-              return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP>;
+              return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP, FUSE>;
             else
-              return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP>;
+              return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP, FUSE>;
           }();
+          BlkFuse<FUSE> fu{};
+          if constexpr (FUSE) fu = *fuse;
           // one launch: every block, its union in windows of umf records where it exceeds
           // the image
           size_t lds = blk_lds(k.umf, k.cq, NT1);
@@ -1812,13 +1859,15 @@ inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs
           hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt, k.ucap,
                              k.snbr, k.sstride, k.rcnt, a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de,
                              a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved, k.uilist,
-                             k.uicnt, k.blist);
+                             k.uicnt, k.blist, fu);
         };
         // (EXP: outputs meaningless, study builds only, make STUDY=1; Monaghan, M_TAIT)
-        if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
-          select_int<0, 1, 2, 3>(exp1, launch);
-        else
-          launch(std::integral_constant<int, 0>{});
+        select_bool(fuse != nullptr, [&](auto fz) {
+          if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
+            select_int<0, 1, 2, 3>(exp1, [&](auto ex) { launch(ex, fz); });
+          else
+            launch(std::integral_constant<int, 0>{}, fz);
+        });
       });
     });
   });

@@ -1115,6 +1115,7 @@ int sph_engine_stats_get(sph_engine *e, sph_engine_stats *st) {
   // (like the other families, not on the single-phase row path, whose flags stay bit 0 alone:
   // sph_engine_csort_paths answers there too)
   if (e->blk || e->mp) st->flags |= e->cs_flags;
+  st->flags |= e->fuse_flag;  // (only ever set on the block path: fuse_step)
   st->inner_refresh = e->inner_refreshes;
   SPH_API_END
 }
@@ -1227,6 +1228,10 @@ int sph_engine_tune(sph_engine *e, int key, int value) {
     case SPH_TUNE_CSORT:
       SPH_REQUIRE(value >= 0 && value <= 2, SPH_HIP_EINVAL, "sph_engine_tune: CSORT %d", value);
       e->csort = value;
+      break;
+    case SPH_TUNE_FUSEINT:
+      SPH_REQUIRE(value == 0 || value == 1, SPH_HIP_EINVAL, "sph_engine_tune: FUSEINT %d", value);
+      e->fuseint = value != 0;
       break;
     default: SPH_REQUIRE(false, SPH_HIP_EINVAL, "sph_engine_tune: unknown key %d", key);
   }

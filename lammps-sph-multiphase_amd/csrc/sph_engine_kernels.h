@@ -219,6 +219,35 @@ static __global__ void k_final_integrate_dt(int n, StepConst sc, double4 *__rest
   final_integrate(n, sc, vr, en, ty, vel, fo, de, rm, dr);
 }
 
+// FixMeso::final_integrate of one step followed by initial_integrate of the next for ONE atom:
+// the arithmetic of k_final_initial and of the block force pass's fused epilogue
+// (sph_blk_kernels.h blk_force_body, FUSE), written once so that both contract the same
+// expressions.  f = {fx, fy, fz, drho} and dei are the step's force and de; x, v (touched only
+// when `moving`: the type is not stationary), vv = {vest, rho} and e are updated in place.
+__device__ __forceinline__ void final_initial_atom(double dtv, double dtf, double m, bool moving,
+                                                   const double4 &f, double dei, double4 &x,
+                                                   double4 &v, double4 &vv, double &e) {
+  e += dtf * dei;           // final
+  vv.w += dtf * f.w;
+  e += dtf * dei;           // initial
+  vv.w += dtf * f.w;
+  if (moving) {
+    const double dtfm = dtf / m;
+    v.x += dtfm * f.x;      // final
+    v.y += dtfm * f.y;
+    v.z += dtfm * f.z;
+    vv.x = v.x + 2.0 * dtfm * f.x;   // initial
+    vv.y = v.y + 2.0 * dtfm * f.y;
+    vv.z = v.z + 2.0 * dtfm * f.z;
+    v.x += dtfm * f.x;
+    v.y += dtfm * f.y;
+    v.z += dtfm * f.z;
+    x.x += dtv * v.x;
+    x.y += dtv * v.y;
+    x.z += dtv * v.z;
+  }
+}
+
 // FixMeso::final_integrate of one step fused with initial_integrate of the next: nothing
 // between them touches these atoms (Verlet::run: output, then the next step's
 // initial_integrate, verlet.cpp:295-307, 230), so one streaming pass does both with the
@@ -238,26 +267,16 @@ static __global__ void k_final_initial(int n, StepConst sc, double4 *__restrict_
   const double4 f = fo[i];
   const double dei = de[i];
   double e = en[i];
-  e += step_dtf(sc, nh) * dei;           // final
-  vv.w += step_dtf(sc, nh) * f.w;
-  e += step_dtf(sc, nh) * dei;           // initial
-  vv.w += step_dtf(sc, nh) * f.w;
-  if (!((sc.stationary_mask >> t) & 1)) {
-    double4 x = xf[i];
-    double4 v = vel[i];
-    const double dtfm = step_dtf(sc, nh) / (rm ? rm[i] : sc.mass[t]);  // rmass if per-atom
-    v.x += dtfm * f.x;      // final
-    v.y += dtfm * f.y;
-    v.z += dtfm * f.z;
-    vv.x = v.x + 2.0 * dtfm * f.x;   // initial
-    vv.y = v.y + 2.0 * dtfm * f.y;
-    vv.z = v.z + 2.0 * dtfm * f.z;
-    v.x += dtfm * f.x;
-    v.y += dtfm * f.y;
-    v.z += dtfm * f.z;
-    x.x += step_dtv(sc, nh) * v.x;
-    x.y += step_dtv(sc, nh) * v.y;
-    x.z += step_dtv(sc, nh) * v.z;
+  const bool moving = !((sc.stationary_mask >> t) & 1);
+  double4 x = make_double4(0.0, 0.0, 0.0, 0.0), v = x;
+  double m = 1.0;
+  if (moving) {
+    x = xf[i];
+    v = vel[i];
+    m = rm ? rm[i] : sc.mass[t];  // rmass if per-atom
+  }
+  final_initial_atom(step_dtv(sc, nh), step_dtf(sc, nh), m, moving, f, dei, x, v, vv, e);
+  if (moving) {
     vel[i] = v;
     xf[i] = x;
     inner_check(sc, i, x);

@@ -216,6 +216,10 @@ struct sph_engine {
   bool ov_ready = false;  // rows_in / rows_bd describe the current list
   bool overlap = false;   // halo/compute overlap (sph_engine_tune SPH_TUNE_OVERLAP)
   int blkumf = 0;         // force pass LDS image cap in records (SPH_TUNE_BLKUMF; 0 = auto)
+  // SPH_TUNE_FUSEINT: the block force pass integrates each row in its epilogue where the step
+  // allows it (fuse_step); fuse_flag: SPH_STAT_FUSEINT if a step of the last run() did
+  bool fuseint = true;
+  int fuse_flag = 0;
   int64_t step = 0;
   int64_t rho_fused_step = -1;  // step whose rhosum/multiphase the list fill summed (k_neigh3 RHO)
   int64_t last_sort = 0;        // step of the last spatial sort of the owned atoms
@@ -254,7 +258,8 @@ struct sph_engine {
   DBuf<double4> vel, fo;
   DBuf<double> de;
   DBuf<int> tag;
-  // sort scratch
+  // sort scratch; xf2 / vr2 are also the second xf / vr pair of a fused step (fuse_step): the
+  // sort needs them only inside a rebuild, the fused force pass only between two
   DBuf<double4> xf2, vr2, vel2;
   DBuf<double> en2;
   DBuf<int> ty2, tag2;
@@ -458,7 +463,8 @@ struct sph_engine {
   int64_t list_entries();
   Row2Args row2_args();
   bool use_row2() const { return row2_fits((long)nlocal + nghost, (long)list_span()); }
-  void pair_compute(bool do_rhosum, bool setup = false);
+  void pair_compute(bool do_rhosum, bool setup = false, bool fuse = false);
+  bool fuse_step() const;
   void setup_forces_full();
   static dim3 mp_rows(int rows) { return dim3((unsigned)(((long long)rows * 8 + 255) / 256)); }
   void pair_compute_mp();

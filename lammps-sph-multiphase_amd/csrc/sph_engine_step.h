@@ -249,7 +249,9 @@ inline Row2Args sph_engine::row2_args() {
 // rhosum (+ the EOS epilogue) -> forward rho -> taitwater[/morris][+heat] on the current
 // list: block path, row path (row2 kernels), or the generic CSR kernels for a list past
 // the row2 kernels' 32-bit offsets.  The setup step's force pass walks the half list.
-inline void sph_engine::pair_compute(bool do_rhosum, bool setup) {
+// fuse (fuse_step): the block force pass integrates each row in its epilogue -- the next
+// step's x and {vest, rho} go to the second pair, which xf and vr name from here on.
+inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse) {
   if (mp) {
     pair_compute_mp();
     return;
@@ -284,6 +286,27 @@ inline void sph_engine::pair_compute(bool do_rhosum, bool setup) {
     launch(k_eos_gas, nall, nall, xf.p, vr.p, en.p, ty.p, dc);
   if (force_mode && setup) {
     setup_forces_full();
+  } else if (force_mode && blk && fuse) {
+    Scope t(this, force_class());  // (this class then includes the integrate)
+    // the second pair at the first's capacity (the sort's twins: grow_twins keeps them so)
+    xf2.reserve_exact(xf.cap);
+    vr2.reserve_exact(vr.cap);
+    BlkFuse<true> fu;
+    fu.sc = sc;
+    // step k's epilogue checks the positions of step k + 1: that step's slot of the flag
+    fu.sc.moved = sc.x0 ? moved.p + ((step + 1) & 1) : nullptr;
+    fu.xn = xf2.p;
+    fu.vn = vr2.p;
+    fu.vel = vel.p;
+    fu.en = en.p;
+    blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args(), &fu);
+    // Everything downstream sees the new pair.  Its ghost records are stale until the next
+    // step's forward comm (k_forward rewrites every ghost's xf, vr and e from its owner) or
+    // rebuild (borders() makes the ghosts anew): a fused step runs no post_force fix, no
+    // refresh and no end-of-step scan behind the pass, and the next step no integrate, so
+    // nothing reads a ghost in between.
+    std::swap(xf, xf2);
+    std::swap(vr, vr2);
   } else if (force_mode && blk) {
     Scope t(this, force_class());
     blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args());
@@ -562,11 +585,25 @@ inline void sph_engine::launch_integrate(bool first, bool chk) {
   });
 }
 
+// Whether a step's force pass may integrate its rows itself (blk_force_body FUSE; the caller
+// excludes the last step of a run(), whose force and de the caller reads): one brick on the
+// block path with taitwater alone -- the heat and gas modes stage e, which the epilogue writes
+// -- and nothing that reads or changes f, de, x or dt between the force pass and the next
+// step's integrate: no post_force fix (setmeso, setforce / addforce), no fix dt/reset, no fix
+// phase_change, no displacement check (check yes: the integrate raises the flag the host reads
+// before it decides on the rebuild).  Asked after the step's rebuild, which decides blk.
+inline bool sph_engine::fuse_step() const {
+  return fuseint && blk && !multi() && !mp && force_mode == M_TAIT && !pc && !nm_check &&
+         !dtr_on && sm.nfix == 0 && ff.nfix == 0 && row2_exp() == 0;
+}
+
 // Verlet::run (verlet.cpp:222-308)
 inline void sph_engine::run(int nsteps) {
   // the final_integrate of step k-1 runs fused with the initial_integrate of step k;
   // the last step's final_integrate runs on its own after the loop
   bool final_done = false;  // (fix dt/reset: the step's final integrate has run already)
+  bool fused = false;       // the previous step's force pass integrated its rows (fuse_step)
+  fuse_flag = 0;
   for (int k = 0; k < nsteps; k++) {
     step++;
     if (sc.x0) sc.moved = moved_flag();
@@ -578,7 +615,8 @@ inline void sph_engine::run(int nsteps) {
     const bool pc_due = pc && step == pc_next;  // (the fix forces this reneighbor)
     const bool elig = !pc_due && neigh_eligible(nm_ago + 1);
     const bool chk = elig && nm_check;
-    launch_integrate(dtr_on ? (k == 0 || final_done) : k == 0, chk);
+    // (a fused step has integrated already, into the pair xf and vr now name)
+    if (!fused) launch_integrate(dtr_on ? (k == 0 || final_done) : k == 0, chk);
     bool build = pc_due;
     if (!pc_due) {
       nm_ago++;
@@ -595,21 +633,34 @@ inline void sph_engine::run(int nsteps) {
       phase_change();
       pc_next += pc_nevery;
     }
+    // (check yes: whether the next step rebuilds is not known yet -- a refresh that a
+    // rebuild then supersedes is harmless, the rebuild clears both slots)
+    auto refresh = [&] {
+      refresh_inner(nm_check ? (pc && step + 1 == pc_next) : (!pc && neigh_eligible(nm_ago + 1)));
+    };
     if (build) {
       rebuild();
       neigh_built();
-      pair_compute(rhosum_due());
-    } else if (ov_ready && rhosum_due() && overlap_on()) {
+    }
+    fused = k + 1 < nsteps && fuse_step();
+    if (!build && !fused && ov_ready && rhosum_due() && overlap_on()) {
       pair_compute_overlap();
     } else {
-      forward();
-      pair_compute(rhosum_due());
+      if (!build) forward();
+      // A fused step refreshes the inner rows BEFORE its passes: the epilogue raises the next
+      // step's slot of the moved flag against x0, so that slot's clear and a due x0 := x of
+      // this step come first, as the unfused order has them (refresh, then the next step's
+      // integrate); and the refresh reads this step's positions, which xf no longer names
+      // behind the pass.  This step's positions are final from the forward comm on, and its
+      // passes read this step's slot, which the refresh leaves as it is: they walk the rows
+      // they would have walked.
+      if (fused) refresh();
+      pair_compute(rhosum_due(), false, fused);
     }
+    if (fused) fuse_flag = SPH_STAT_FUSEINT;
     post_force_setmeso();
     post_force_forcefix();
-    // (check yes: whether the next step rebuilds is not known yet -- a refresh that a
-    // rebuild then supersedes is harmless, the rebuild clears both slots)
-    refresh_inner(nm_check ? (pc && step + 1 == pc_next) : (!pc && neigh_eligible(nm_ago + 1)));
+    if (!fused) refresh();
     if (timing && pending.size() > 4096) harvest();
     // fix dt/reset: Modify::end_of_step follows the final integrate of a step with
     // ntimestep % nevery == 0 (modify.cpp:404-408, verlet.cpp:299), and the next initial
