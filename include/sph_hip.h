@@ -524,6 +524,46 @@ typedef struct {
 } sph_dt_stats;
 int sph_engine_dt_stats(sph_engine *e, sph_dt_stats *out);
 
+/* thermo's `press` and fix gravity's scalar (`f_gfix`, so v_etot = c_esph + ke + f_gfix) without
+   a sph_engine_get_atoms round trip: the pair virial, the kinetic sums and the gravity energy
+   on the device (single-phase engines: sph/taitwater[/morris], + sph/heatconduction, which
+   adds no force and so no virial, and sph/idealgas).
+   sph_engine_virial_every(e, nevery): the virial is due on the setup step, on every step with
+   step % nevery == 0 and on the last step of each sph_engine_run call, as LAMMPS' thermo
+   output is; 0 = never (the default).  On a due step the force pass of whichever path runs
+   (block, row, generic CSR; the setup step's pass too) is its virial instantiation: each
+   owned row i also sums w_i[ab] = sum_j del_a del_b fpair_ij over the neighbours it accepts
+   (del = x_i - x_j, fpair as the row's force has it) into a scratch row, and a fixed-shape
+   two-stage fold leaves this rank's W = 1/2 sum_i w_i -- every pair once over all bricks,
+   the value of the reference's newton-on run (vflag_fdotr: virial_fdotr_compute,
+   pair.cpp:1403-1420; sph/idealgas' doubled ev_tally does not reach it).  One exception:
+   sph/taitwater/morris' force also has the part vel * fvisc, which is not along del, so the
+   reference's x . f carries sum del_a vel_b fvisc besides; the engine tallies the fpair part
+   alone (what ev_tally would), and a press formed from it lacks that shear term.  No atomics: two
+   runs from one state give the same bits.  A step that is not due launches exactly what an
+   engine without this call launches; a due step runs unfused (SPH_TUNE_FUSEINT) and without
+   the halo overlap, and the fields after it are bit for bit those of a run that never asked.
+   No fix of the package contributes a virial.  Before sph_engine_setup.  SPH_HIP_EINVAL:
+   nevery < 0, after setup, a multiphase engine (cfg->mp: those styles' virial is not restated).
+   sph_engine_thermo(e, mvv2e, nktv2p, out): after setup, any engine.  The sums run over the
+   owned atoms in the state sph_engine_get_atoms would return (v is atom->v, m = mass[type],
+   rmass on a multiphase engine).  If virial_step is not the current step, press is NaN; the
+   other fields are valid.  Ranks: the caller sums virial, ke_tensor, ke and egrav and forms
+   press again, as for sph_engine_reduce.  Not covered: per-atom stress, thermo_modify norm. */
+int sph_engine_virial_every(sph_engine *e, int nevery);
+typedef struct {
+  int64_t virial_step;   /* step whose force pass tallied virial[] (-1: none yet) */
+  double virial[6];      /* this rank's share, xx yy zz xy xz yz */
+  double ke_tensor[6];   /* sum m v_a v_b * mvv2e over owned atoms (v, not vest) */
+  double ke;             /* 0.5 sum m |v|^2 * mvv2e */
+  double egrav;          /* this rank's share of f_gfix: -sum m (g . x) over the types of
+                            cfg->gravity_mask (fix_gravity.cpp:272-291) */
+  double volume;         /* xprd*yprd(*zprd in 3-D) of the global box */
+  double press;          /* (sum m v^2 * mvv2e + W_xx + W_yy [+ W_zz]) / (dim * volume) * nktv2p
+                            from this rank's sums (compute_pressure.cpp:193-207) */
+} sph_thermo_out;
+int sph_engine_thermo(sph_engine *e, double mvv2e, double nktv2p, sph_thermo_out *out);
+
 /* Static regions (box units), shared by the clamps and the reductions below.  The
    predicates are LAMMPS' own, closed boundaries included: sphere
    sqrt(dx*dx+dy*dy+dz*dz) <= radius (region_sphere.cpp:96-105), block x >= xlo && x <= xhi

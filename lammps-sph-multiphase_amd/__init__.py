@@ -116,6 +116,14 @@ class DtStats(C.Structure):
                 ("changes", C.c_int64)]
 
 
+class ThermoOut(C.Structure):
+    """sph_thermo_out: the pair virial of the last due step, the kinetic sums, fix gravity's
+    scalar, the box volume and compute pressure's scalar (NaN while the virial is stale)"""
+    _fields_ = [("virial_step", C.c_int64), ("virial", C.c_double * 6),
+                ("ke_tensor", C.c_double * 6), ("ke", C.c_double), ("egrav", C.c_double),
+                ("volume", C.c_double), ("press", C.c_double)]
+
+
 SPH_REGION_SPHERE, SPH_REGION_BLOCK = 0, 1
 SPH_SET_RHO, SPH_SET_E, SPH_SET_T, SPH_SET_DE = 0, 1, 2, 3
 SPH_Q_ONE, SPH_Q_RHO, SPH_Q_E, SPH_Q_T, SPH_Q_DE, SPH_Q_MASS, SPH_Q_KE = range(7)
@@ -337,6 +345,8 @@ EXPORTS = {
     "sph_engine_neigh_stats": (_i, [_vp, C.POINTER(NeighStats)]),
     "sph_engine_dt_reset": (_i, [_vp, C.POINTER(DtReset)]),
     "sph_engine_dt_stats": (_i, [_vp, C.POINTER(DtStats)]),
+    "sph_engine_virial_every": (_i, [_vp, _i]),
+    "sph_engine_thermo": (_i, [_vp, C.c_double, C.c_double, C.POINTER(ThermoOut)]),
     "sph_engine_get_atoms_multiphase": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sph_engine_write_restart": (_i, [_vp, _vp, C.c_int64, C.POINTER(_i)]),
     "sph_engine_read_restart": (_i, [_vp, _i, _dp]),
@@ -805,6 +815,22 @@ class Engine:
         _chk(self.L.sph_engine_dt_stats(self.h, C.byref(st)))
         return dict(dt=float(st.dt), time=float(st.time), laststep=int(st.laststep),
                     changes=int(st.changes))
+
+    def virial_every(self, n):
+        """The pair virial is tallied by the force pass of the setup step, of every step with
+        step % n == 0 and of the last step of each run() (0 = never, the default); before
+        setup(), single-phase engines only (sph_engine_virial_every)"""
+        _chk(self.L.sph_engine_virial_every(self.h, int(n)))
+
+    def thermo(self, mvv2e=1.0, nktv2p=1.0) -> dict:
+        """sph_engine_thermo, after setup(): virial_step, virial[6] (xx yy zz xy xz yz, this
+        rank's share, every pair once over all ranks), ke_tensor[6], ke, egrav (f_gfix), volume
+        and press -- NaN unless virial_step is the current step"""
+        o = ThermoOut()
+        _chk(self.L.sph_engine_thermo(self.h, float(mvv2e), float(nktv2p), C.byref(o)))
+        return dict(virial_step=int(o.virial_step), virial=np.array(o.virial[:], dtype=np.float64),
+                    ke_tensor=np.array(o.ke_tensor[:], dtype=np.float64), ke=float(o.ke),
+                    egrav=float(o.egrav), volume=float(o.volume), press=float(o.press))
 
     def setmeso(self, what, value, types=None, region=None, noregion=None):
         """fix setmeso meso_rho|meso_e|meso_t value [region|noregion R] / fix setmesode value

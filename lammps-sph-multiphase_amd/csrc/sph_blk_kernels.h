@@ -1248,6 +1248,12 @@ k_blk_inner(int n, const int *__restrict__ ulist, const int *__restrict__ ucnt, 
 // pair (xn, vn: the pass still reads other rows' records of this step from xf and vr), v and e
 // in place.  The heat and gas modes stage their neighbours' e, which the epilogue would
 // overwrite under them: they would need e in two buffers as well and stay unfused.
+// VIR (the engine's due steps; never with FUSE -- a due step runs unfused): the walk also
+// tallies the row's share of the pair virial, w_i[ab] = sum_j del_a del_b fpair_ij, with the
+// fpair factor sp of the row's force (one type: scaled by m_i m_j wK at the end, as F is), and
+// the row-leader lane stores it to vir.w[6 row ..] (xx yy zz xy xz yz).  The six accumulators
+// cost registers, so the variant never takes the six-wave kernel; the plain instantiation takes
+// an empty RowVir and is the kernel it was.
 template <bool FUSE>
 struct BlkFuse {};
 template <>
@@ -1266,15 +1272,18 @@ struct BlkFuse<true> {
       double gx, double gy, double gz, int um, int cq,                                        \
       const unsigned short *__restrict__ snbi, const int *__restrict__ icnt,                  \
       const int *__restrict__ moved, const int *__restrict__ uilist,                          \
-      const int *__restrict__ uicnt, const int *__restrict__ blist, BlkFuse<FUSE> fu
+      const int *__restrict__ uicnt, const int *__restrict__ blist, BlkFuse<FUSE> fu,         \
+      RowVir<VIR> vir
 #define SPH_BLK_FORCE_ARGS                                                                \
   n, ulist, ucnt, ucap, snbr, sstride, rcnt, xf, vr, ty, en, cf, fo, de, gx, gy, gz, um, cq, \
-      snbi, icnt, moved, uilist, uicnt, blist, fu
+      snbi, icnt, moved, uilist, uicnt, blist, fu, vir
 // (the body of the force pass; the kernels below differ only in their occupancy request)
 template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, int AHEAD = 1,
-          bool FUSE = false>
+          bool FUSE = false, bool VIR = false>
 __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   static_assert(!FUSE || (MODE == M_TAIT && EXP == 0), "FUSE: taitwater alone");
+  static_assert(!VIR || ((MODE & (M_TAIT | M_GAS)) != 0 && EXP == 0 && !FUSE),
+                "VIR: a force body, unfused");
   if (snbi && *moved == 0) {  // (workgroup-uniform) the inner rows are still exact
     snbr = snbi;
     rcnt = icnt;
@@ -1381,6 +1390,19 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
   // the heat terms.  One type: sp = (P_i/rho_i^2 + P_j/rho_j^2 [+ fvisc]) w, the row's
   // factors applied at the end; several types: sp, sv, D and EH terms carry them per pair.
   double fx = 0.0, fy = 0.0, fz = 0.0, D = 0.0, E = 0.0, EH = 0.0;
+  double wv[6] = {};  // (the virial variant's; dead code otherwise)
+  auto tally = [&](double dx, double dy, double dz, double sp) {
+    // opaque copies: the tally must not take part in how the compiler contracts the force's
+    // own products into FMAs (the Morris variant otherwise differed from the plain kernel in
+    // the last bit of f), so that a due step leaves the fields a plain step leaves
+    asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz), "+v"(sp));
+    wv[0] += dx * dx * sp;
+    wv[1] += dy * dy * sp;
+    wv[2] += dz * dz * sp;
+    wv[3] += dx * dy * sp;
+    wv[4] += dx * dz * sp;
+    wv[5] += dy * dz * sp;
+  };
   auto load = [&](int q) {
     const unsigned char *const rec = blk_smem + q * 16;
     BlkRec r;
@@ -1434,12 +1456,14 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
         tfy = dy * sp;
         tfz = dz * sp;
         tE = sp * dvdr;
+        if constexpr (VIR) tally(dx, dy, dz, sp);
       } else if (VISC == BLK_VISC_NONE) {  // (one type, Monaghan with viscC = 0)
         const double sp = (xi.w + a1.y) * w;
         tfx = dx * sp;
         tfy = dy * sp;
         tfz = dz * sp;
         tE = sp * dvdr;
+        if constexpr (VIR) tally(dx, dy, dz, sp);
       } else {
         const double sp = NT1 ? (xi.w + a1.y) * w : cc.mm * ((xi.w + a1.y) * w);
         const double cv = cc.viscC * rcp1(vi.w * a3.y);
@@ -1448,6 +1472,7 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
         tfy = dy * sp - vely * sv;
         tfz = dz * sp - velz * sv;
         tE = sp * dvdr - sv * (velx * velx + vely * vely + velz * velz);
+        if constexpr (VIR) tally(dx, dy, dz, sp);
       }
       tD = NT1 ? dvdr * w : cc.mj * (dvdr * w);
       fx += tfx;
@@ -1535,11 +1560,21 @@ __device__ __forceinline__ void blk_force_body(SPH_BLK_FORCE_PARAMS) {
       de[row] = dE;
     }
   }
+  if constexpr (VIR) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) wv[k] = group_sum<G>(wv[k]);
+    if (lane == 0 && live) {
+      const double g = NT1 ? t1.mm * t1.wK : 1.0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) vir.w[(size_t)row * 6 + k] = g * wv[k];
+    }
+  }
 }
 
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false>
+template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false,
+          bool VIR = false>
 __global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
-  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 1, FUSE>(SPH_BLK_FORCE_ARGS);
+  blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 1, FUSE, VIR>(SPH_BLK_FORCE_ARGS);
 }
 // one type, taitwater alone (C2): asked for 6 waves per SIMD (<= 80 VGPRs: what the 49 KiB
 // image allows, three workgroups per CU) with no records read ahead -- the other waves cover
@@ -1548,9 +1583,11 @@ __global__ void __launch_bounds__(R * G) k_blk_force(SPH_BLK_FORCE_PARAMS) {
 // 0.2497 vs 0.2632 / 0.2627 ms against that (profiles/r05/README.md).  The heat and
 // multi-type variants keep the default (at 96 VGPRs they would spill), and so does the gas
 // mode (M_GAS: the heat-size image and one more operand per pair).
-template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false>
+template <int R, int G, int U, int NCH, int VISC, int MODE, bool NT1, int EXP = 0, bool FUSE = false,
+          bool VIR = false>
 __global__ void __launch_bounds__(R * G) __attribute__((amdgpu_waves_per_eu(6, 6)))
 k_blk_force_w6(SPH_BLK_FORCE_PARAMS) {
+  static_assert(!VIR, "the virial variant keeps the default occupancy");
   blk_force_body<R, G, U, NCH, VISC, MODE, NT1, EXP, 0, FUSE>(SPH_BLK_FORCE_ARGS);
 }
 
@@ -1816,15 +1853,19 @@ inline void blk_inner(bool nt1, hipStream_t s, const BlkArgs &k, const double4 *
   });
 }
 
-// fuse != nullptr: the pass integrates each row in its epilogue (BlkFuse; M_TAIT alone)
+// fuse != nullptr: the pass integrates each row in its epilogue (BlkFuse; M_TAIT alone);
+// vw != nullptr: the virial variant (RowVir; the modes with a force body, never fused)
 inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs &k,
-                      const RowArgs &a, const BlkFuse<true> *fuse = nullptr) {
+                      const RowArgs &a, const BlkFuse<true> *fuse = nullptr,
+                      double *vw = nullptr) {
   if (k.n == 0) return;
+  SPH_REQUIRE(!vw || (!fuse && (mode & (M_TAIT | M_GAS))), SPH_HIP_EINVAL,
+              "blk_force: the virial variant is unfused and needs a force body (mode %d)", mode);
   SPH_REQUIRE(!fuse || (mode == M_TAIT && (!nt1 || k.exp == 0)), SPH_HIP_EINVAL,
               "blk_force: the fused integrate exists for taitwater alone (mode %d)", mode);
   // BLK_VISC_NONE and the study variants are for one type
   const int visc1 = (visc == BLK_VISC_NONE && !nt1) ? SPH_VISC_MONAGHAN : visc;
-  const int exp1 = nt1 ? k.exp : 0;
+  const int exp1 = (nt1 && !vw) ? k.exp : 0;
   blk_select(nt1, k, [&](auto sh, auto t, auto nch) {
     constexpr int R = sh.v[0], G = sh.v[1], U = sh.v[2], NCH = nch;
     constexpr bool NT1 = t;
@@ -1835,17 +1876,21 @@ inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs
         // M_TAIT alone
         constexpr int VISC = (MODE == M_TAIT || (vc == SPH_VISC_MORRIS && (MODE & M_TAIT)))
                                  ? (int)vc : SPH_VISC_MONAGHAN;
-        auto launch = [&](auto ex, auto fz) {
+        auto launch = [&](auto ex, auto fz, auto vi) {
           constexpr int EXP = ex;
           constexpr bool FUSE = decltype(fz)::value && MODE == M_TAIT && EXP == 0;
+          constexpr bool VIR =
+              decltype(vi)::value && !FUSE && (MODE & (M_TAIT | M_GAS)) != 0 && EXP == 0;
           auto fn = [] {
-            if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0)
+            if constexpr (NT1 && MODE == M_TAIT && EXP == 0 && NCH > 0 && !VIR)
               return k_blk_force_w6<R, G, U, NCH, VISC, MODE, NT1, EXP, FUSE>;
             else
-              return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP, FUSE>;
+              return k_blk_force<R, G, U, NCH, VISC, MODE, NT1, EXP, FUSE, VIR>;
           }();
           BlkFuse<FUSE> fu{};
           if constexpr (FUSE) fu = *fuse;
+          RowVir<VIR> vir{};
+          if constexpr (VIR) vir.w = vw;
           // one launch: every block, its union in windows of umf records where it exceeds
           // the image
           size_t lds = blk_lds(k.umf, k.cq, NT1);
@@ -1859,14 +1904,18 @@ inline void blk_force(bool nt1, int visc, int mode, hipStream_t s, const BlkArgs
           hipLaunchKernelGGL(fn, dim3(nb), dim3(R * G), lds, s, k.n, k.ulist, k.ucnt, k.ucap,
                              k.snbr, k.sstride, k.rcnt, a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de,
                              a.gx, a.gy, a.gz, k.umf, k.cq, k.snbi, k.icnt, k.moved, k.uilist,
-                             k.uicnt, k.blist, fu);
+                             k.uicnt, k.blist, fu, vir);
         };
         // (EXP: outputs meaningless, study builds only, make STUDY=1; Monaghan, M_TAIT)
-        select_bool(fuse != nullptr, [&](auto fz) {
+        // (fused and virial exclude each other: one selector over {plain, fused, virial})
+        select_int<0, 1, 2>(fuse ? 1 : vw ? 2 : 0, [&](auto wh) {
+          constexpr int WH = wh;
+          constexpr std::bool_constant<WH == 1> fz{};
+          constexpr std::bool_constant<WH == 2> vi{};
           if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
-            select_int<0, 1, 2, 3>(exp1, [&](auto ex) { launch(ex, fz); });
+            select_int<0, 1, 2, 3>(exp1, [&](auto ex) { launch(ex, fz, vi); });
           else
-            launch(std::integral_constant<int, 0>{}, fz);
+            launch(std::integral_constant<int, 0>{}, fz, vi);
         });
       });
     });

@@ -60,8 +60,10 @@ struct ForceArgs {
   const double4 *vso = nullptr, *vsg = nullptr;
 };
 
+// vir (the engine's due steps; full lists with a force body): a.virial is the per-row scratch
+// of k_force's VIR
 inline void launch_force(int dim, bool nt1, hipStream_t s, int visc, int mode,
-                         const ForceArgs &a) {
+                         const ForceArgs &a, bool vir = false) {
   if (a.inum <= 0) return;
   select_int<8, 4, 16>(group_lanes(), [&](auto g) {
     constexpr int G = g;
@@ -78,11 +80,17 @@ inline void launch_force(int dim, bool nt1, hipStream_t s, int visc, int mode,
             select_bool(visc == SPH_VISC_MORRIS, [&](auto mor) {
               // Morris viscosity exists only for the modes with M_TAIT
               constexpr int VISC = (mor && (MODE & M_TAIT)) ? 1 : 0;
-              hipLaunchKernelGGL((k_force<G, DIM, VISC, MODE, NT1>),
-                                 dim3(grid_for_rows(a.inum, G)), dim3(256), 0, s, a.inum,
-                                 a.nlocal, a.newton, a.ilist, a.off, a.nbr, a.xf, a.vr, a.ty,
-                                 a.en, a.fo, a.de, a.accum, a.cf, a.gx, a.gy, a.gz, a.virial,
-                                 a.nojside, a.vso, a.vsg);
+              constexpr bool CANVIR = (MODE & (M_TAIT | M_GAS)) != 0 && (MODE & M_HALF) == 0;
+              SPH_REQUIRE(!vir || CANVIR, SPH_HIP_EINVAL, "no virial variant of force mode %d",
+                          mode);
+              select_bool(vir, [&](auto vi) {
+                constexpr bool VIR = vi && CANVIR;
+                hipLaunchKernelGGL((k_force<G, DIM, VISC, MODE, NT1, VIR>),
+                                   dim3(grid_for_rows(a.inum, G)), dim3(256), 0, s, a.inum,
+                                   a.nlocal, a.newton, a.ilist, a.off, a.nbr, a.xf, a.vr, a.ty,
+                                   a.en, a.fo, a.de, a.accum, a.cf, a.gx, a.gy, a.gz, a.virial,
+                                   a.nojside, a.vso, a.vsg);
+              });
             });
           }
         });

@@ -985,6 +985,60 @@ int sph_engine_dt_stats(sph_engine *e, sph_dt_stats *out) {
   SPH_API_END
 }
 
+int sph_engine_virial_every(sph_engine *e, int nevery) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e, SPH_HIP_EINVAL, "sph_engine_virial_every: NULL engine");
+  SPH_REQUIRE(nevery >= 0, SPH_HIP_EINVAL, "sph_engine_virial_every: nevery %d < 0", nevery);
+  SPH_REQUIRE(!e->setup_done, SPH_HIP_EINVAL,
+              "sph_engine_virial_every: before sph_engine_setup (the setup step's force pass "
+              "tallies the first virial)");
+  SPH_REQUIRE(!e->mp, SPH_HIP_EINVAL,
+              "sph_engine_virial_every: the multiphase styles have no virial here "
+              "(sph_engine_thermo still gives their kinetic and gravity sums)");
+  e->vir_every = nevery;
+  SPH_API_END
+}
+
+int sph_engine_thermo(sph_engine *e, double mvv2e, double nktv2p, sph_thermo_out *out) {
+  SPH_API_BEGIN
+  SPH_REQUIRE(e && out, SPH_HIP_EINVAL, "sph_engine_thermo: NULL argument");
+  SPH_REQUIRE(e->setup_done, SPH_HIP_EINVAL, "sph_engine_thermo: call sph_engine_setup first");
+  SPH_HIP_TRY(hipSetDevice(e->device));
+  const int n = e->nlocal;
+  double th[TH_NS] = {}, w[VIR_NS] = {};
+  const int nb = (int)std::min<long>(blocks(n), RED_MAXBLOCKS);
+  if (nb) {
+    e->vir_part.reserve((size_t)RED_MAXBLOCKS * TH_NS);
+    e->th_tot.reserve(TH_NS);
+    hipLaunchKernelGGL(k_thermo_part, dim3(nb), dim3(RED_THREADS), 0, e->s, n, e->xf.p, e->ty.p,
+                       e->vel.p, e->mp ? (const double *)e->rm.p : nullptr, e->type_mass(),
+                       e->cfg.gravity_mask, e->cfg.gravity[0], e->cfg.gravity[1],
+                       e->cfg.gravity[2], e->vir_part.p);
+    hipLaunchKernelGGL(k_slots_final, dim3(1), dim3(64), 0, e->s, nb, TH_NS, 1.0, e->vir_part.p,
+                       e->th_tot.p);
+    SPH_HIP_TRY(hipGetLastError());
+    e->to_host(th, e->th_tot.p, TH_NS);
+  }
+  if (e->vir_step >= 0) e->to_host(w, e->vir_tot.p, VIR_NS);
+  SPH_HIP_TRY(hipStreamSynchronize(e->s));
+  out->virial_step = e->vir_step;
+  for (int k = 0; k < 6; k++) {
+    out->virial[k] = w[k];
+    out->ke_tensor[k] = th[k] * mvv2e;
+  }
+  out->ke = th[6] * mvv2e;
+  out->egrav = th[7];
+  const int dim = e->cfg.dim;
+  out->volume = e->box.prd[0] * e->box.prd[1] * (dim == 3 ? e->box.prd[2] : 1.0);
+  // ComputePressure::compute_scalar (compute_pressure.cpp:193-207) with keflag: dof * boltz * t
+  // of compute temp is sum m |v|^2 * mvv2e
+  const double trace = w[0] + w[1] + (dim == 3 ? w[2] : 0.0);
+  out->press = (e->vir_step >= 0 && e->vir_step == e->step)
+                   ? (2.0 * out->ke + trace) / ((double)dim * out->volume) * nktv2p
+                   : std::nan("");
+  SPH_API_END
+}
+
 int sph_engine_pair_passes(sph_engine *e, int n) {
   SPH_API_BEGIN
   SPH_REQUIRE(e && n >= 0, SPH_HIP_EINVAL, "sph_engine_pair_passes: bad argument");

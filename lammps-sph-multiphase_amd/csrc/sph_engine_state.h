@@ -182,6 +182,14 @@ struct sph_engine {
   DBuf<double> pf_sum;
   // sph_engine_moments / sph_engine_gyration: the blocks' partials, then the folded results
   DBuf<double> mom_buf;
+  // the pair virial (sph_engine_virial_every; single-phase engines): due on the setup step,
+  // on steps with step % vir_every == 0 and on the last step of each run().  A due step's
+  // force pass stores each owned row's share in vir_w (six doubles per row), virial_fold()
+  // leaves this rank's W in vir_tot and names the step in vir_step; sph_engine_thermo's
+  // kinetic and gravity sums share vir_part and leave theirs in th_tot
+  int vir_every = 0;
+  int64_t vir_step = -1;
+  DBuf<double> vir_w, vir_part, vir_tot, th_tot;
   bool pc_tags_agreed = false;  // bricks: tag_next agreed over the ranks (first call)
   std::vector<double> cv_by_tag;  // single-phase engines: the constant cv, for restarts
 
@@ -463,9 +471,12 @@ struct sph_engine {
   int64_t list_entries();
   Row2Args row2_args();
   bool use_row2() const { return row2_fits((long)nlocal + nghost, (long)list_span()); }
-  void pair_compute(bool do_rhosum, bool setup = false, bool fuse = false);
+  void pair_compute(bool do_rhosum, bool setup = false, bool fuse = false, bool vir = false);
   bool fuse_step() const;
-  void setup_forces_full();
+  void setup_forces_full(double *vw);
+  bool force_body() const { return (force_mode & (M_TAIT | M_GAS)) != 0; }
+  double *virial_rows();
+  void virial_fold();
   static dim3 mp_rows(int rows) { return dim3((unsigned)(((long long)rows * 8 + 255) / 256)); }
   void pair_compute_mp();
   double uniform_cv(const char *who) const;

@@ -251,7 +251,10 @@ inline Row2Args sph_engine::row2_args() {
 // the row2 kernels' 32-bit offsets.  The setup step's force pass walks the half list.
 // fuse (fuse_step): the block force pass integrates each row in its epilogue -- the next
 // step's x and {vest, rho} go to the second pair, which xf and vr name from here on.
-inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse) {
+// vir (a due step of sph_engine_virial_every, never fused): the force pass is the VIR
+// instantiation of whichever path runs, and virial_fold() follows it.
+inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse, bool vir) {
+  SPH_REQUIRE(!vir || (!fuse && !mp), SPH_HIP_ERUNTIME, "a virial step is unfused, single-phase");
   if (mp) {
     pair_compute_mp();
     return;
@@ -284,8 +287,10 @@ inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse) {
   // not rhosum was due
   if ((force_mode & M_GAS) && nall)
     launch(k_eos_gas, nall, nall, xf.p, vr.p, en.p, ty.p, dc);
+  // the rows' shares of a due step (nullptr: not due, or no style with a force body)
+  double *const vw = (vir && force_body()) ? virial_rows() : nullptr;
   if (force_mode && setup) {
-    setup_forces_full();
+    setup_forces_full(vw);
   } else if (force_mode && blk && fuse) {
     Scope t(this, force_class());  // (this class then includes the integrate)
     // the second pair at the first's capacity (the sort's twins: grow_twins keeps them so)
@@ -309,17 +314,44 @@ inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse) {
     std::swap(vr, vr2);
   } else if (force_mode && blk) {
     Scope t(this, force_class());
-    blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args());
+    blk_force(nt1(), blk_visc(), force_mode, s, blk_args(), row_args(), nullptr, vw);
   } else if (force_mode && use_row2()) {
     Scope t(this, force_class());
-    row2_force(nt1(), row_visc(), force_mode, s, row2_args());
+    row2_force(nt1(), row_visc(), force_mode, s, row2_args(), vw);
   } else if (force_mode) {
     Scope t(this, force_class());
-    launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, force_args());
+    ForceArgs a = force_args();
+    a.virial = vw;
+    launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a, vw != nullptr);
   } else {
     SPH_HIP_TRY(hipMemsetAsync(fo.p, 0, nlocal * sizeof(double4), s));
     SPH_HIP_TRY(hipMemsetAsync(de.p, 0, nlocal * sizeof(double), s));
   }
+  if (vir) virial_fold();
+}
+
+// the due step's scratch: six doubles per owned row, which the VIR force pass writes whole
+inline double *sph_engine::virial_rows() {
+  vir_w.reserve_min1((size_t)VIR_NS * nlocal);
+  return vir_w.p;
+}
+// W = 1/2 sum over the owned rows of their shares (each pair is seen from both of its rows,
+// on this brick or another: summed over the bricks every pair counts once), folded in
+// k_reduce_part's fixed shape into vir_tot; zeros for an engine whose styles have no force
+// body (heat conduction alone) or a brick without atoms
+inline void sph_engine::virial_fold() {
+  vir_tot.reserve(VIR_NS);
+  const int nb = (int)std::min<long>(blocks(nlocal), RED_MAXBLOCKS);
+  if (!force_body() || nb == 0) {
+    SPH_HIP_TRY(hipMemsetAsync(vir_tot.p, 0, VIR_NS * sizeof(double), s));
+  } else {
+    vir_part.reserve((size_t)RED_MAXBLOCKS * TH_NS);
+    hipLaunchKernelGGL(k_virial_part, dim3(nb), dim3(RED_THREADS), 0, s, nlocal, vir_w.p,
+                       vir_part.p);
+    hipLaunchKernelGGL(k_slots_final, dim3(1), dim3(64), 0, s, nb, VIR_NS, 0.5, vir_part.p,
+                       vir_tot.p);
+  }
+  vir_step = step;
 }
 
 // Force pass of Verlet::setup with the reference's half-list ownership (see
@@ -329,7 +361,7 @@ inline void sph_engine::pair_compute(bool do_rhosum, bool setup, bool fuse) {
 // was bordered.  Walked as a full-list gather (the global-index CSR rows of the setup
 // build) that picks, for each ghost pair, the vest pair the reference's one evaluation
 // uses (k_force: vso / vsg) -- no half list, no atomics, no reverse comm.
-inline void sph_engine::setup_forces_full() {
+inline void sph_engine::setup_forces_full(double *vw) {
   const int n = nlocal, nall = nlocal + nghost;
   if (force_mode == 0 || n == 0) return;
   vsg.reserve_min1(nghost);
@@ -341,7 +373,8 @@ inline void sph_engine::setup_forces_full() {
   ForceArgs a = force_args();
   a.vso = vso.p;
   a.vsg = vsg.p;
-  launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a);
+  a.virial = vw;  // (the rows' shares of the setup step's virial, or nullptr)
+  launch_force(cfg.dim, nt1(), s, row_visc(), force_mode, a, vw != nullptr);
 }
 
 // ---- multiphase stack -------------------------------------------------------------
@@ -530,6 +563,7 @@ inline bool sph_engine::rhosum_due() const {
 // Verlet::setup (verlet.cpp:88-139)
 inline void sph_engine::setup() {
   step = 0;
+  vir_step = -1;  // (step starts over: no earlier virial may pass for this run's)
   Scope t(this, T_NEIGH);
   if (pc) {  // (every setup sorts: verlet.cpp:106)
     if (!lidx_valid) lidx_from_tags();
@@ -542,7 +576,7 @@ inline void sph_engine::setup() {
   if (nlocal)
     dev_copy(vso.p, vr.p, (size_t)nlocal);
   launch(k_vest_from_v, nlocal, nlocal, cfg.stationary_mask, ty.p, vel.p, vr.p);
-  pair_compute(rhosum_due(), /*setup=*/true);
+  pair_compute(rhosum_due(), /*setup=*/true, false, vir_every > 0);
   post_force_setmeso();  // (FixSetMeso::setup calls post_force)
   if (ff_tally) {
     ff_tot.reserve(FF_NT);
@@ -642,8 +676,12 @@ inline void sph_engine::run(int nsteps) {
       rebuild();
       neigh_built();
     }
-    fused = k + 1 < nsteps && fuse_step();
-    if (!build && !fused && ov_ready && rhosum_due() && overlap_on()) {
+    // the virial is due as thermo output is (every vir_every steps and on a run's last step);
+    // a due step runs unfused and without the halo overlap, whose per-row arithmetic is the
+    // same, so the fields do not depend on vir_every
+    const bool vdue = vir_every > 0 && (step % vir_every == 0 || k + 1 == nsteps);
+    fused = k + 1 < nsteps && fuse_step() && !vdue;
+    if (!build && !fused && !vdue && ov_ready && rhosum_due() && overlap_on()) {
       pair_compute_overlap();
     } else {
       if (!build) forward();
@@ -655,7 +693,7 @@ inline void sph_engine::run(int nsteps) {
       // passes read this step's slot, which the refresh leaves as it is: they walk the rows
       // they would have walked.
       if (fused) refresh();
-      pair_compute(rhosum_due(), false, fused);
+      pair_compute(rhosum_due(), false, fused, vdue);
     }
     if (fused) fuse_flag = SPH_STAT_FUSEINT;
     post_force_setmeso();

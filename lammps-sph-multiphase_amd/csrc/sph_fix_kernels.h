@@ -190,6 +190,85 @@ static __global__ void k_reduce_final(int nblocks, int nsel, const ReducePart *_
   out[s].count = p.cnt;
 }
 
+// ---- thermo sums (sph_engine_thermo) -----------------------------------------------------------
+// The pair virial of a due step and the kinetic and gravity sums, in k_reduce_part's fixed
+// shape: stage 1 leaves part[block * NS + j], the one-block stage 2 folds the blocks in block
+// order.  No atomics; the bits depend on (n, grid) alone.
+constexpr int VIR_NS = 6;  // xx yy zz xy xz yz
+constexpr int TH_NS = 8;   // sum m v_a v_b (the same six), sum m |v|^2 / 2, -sum m (g . x)
+
+// the block's fold of each thread's NS accumulators: shuffles, then the waves through LDS
+template <int NS>
+__device__ __forceinline__ void slots_block_fold(const double (&acc)[NS],
+                                                 double *__restrict__ part) {
+  __shared__ double s_p[RED_THREADS / 64][NS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < NS; j++) {
+    double p = acc[j];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) p += __shfl_down(p, d, 64);
+    if (lane == 0) s_p[wave][j] = p;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < NS) {
+    double p = s_p[0][threadIdx.x];
+    for (int w = 1; w < RED_THREADS / 64; w++) p += s_p[w][threadIdx.x];
+    part[(size_t)blockIdx.x * NS + threadIdx.x] = p;
+  }
+}
+
+// stage 1 of the virial: the owned rows' shares w[6 i ..] as the force pass stored them
+// (k_force / k_row2_force / blk_force_body VIR), each thread its grid-stride slice in row order
+static __global__ void __launch_bounds__(RED_THREADS)
+k_virial_part(int n, const double *__restrict__ w, double *__restrict__ part) {
+  double acc[VIR_NS] = {};
+  const int stride = gridDim.x * blockDim.x;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+#pragma unroll
+    for (int j = 0; j < VIR_NS; j++) acc[j] += w[(size_t)i * VIR_NS + j];
+  }
+  slots_block_fold<VIR_NS>(acc, part);
+}
+
+// stage 1 of the kinetic and gravity sums over the owned atoms: v is atom->v (not vest), x the
+// wrapped position, m = rmass (rm != nullptr) or mass[type]; gmask: the types of the gravity
+// fix's group (cfg.gravity_mask, 0 = every type).  FixGravity::compute_scalar
+// (fix_gravity.cpp:272-291): egrav -= massone * (xacc x + yacc y + zacc z).
+static __global__ void __launch_bounds__(RED_THREADS)
+k_thermo_part(int n, const double4 *__restrict__ xf, const int *__restrict__ ty,
+              const double4 *__restrict__ vel, const double *__restrict__ rm, StepMass sm,
+              int gmask, double gx, double gy, double gz, double *__restrict__ part) {
+  double acc[TH_NS] = {};
+  const int stride = gridDim.x * blockDim.x;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int t = ty[i];
+    const double4 x = xf[i];
+    const double4 v = vel[i];
+    const double m = rm ? rm[i] : sm.mass[t];
+    const double mg = (gmask == 0 || ((gmask >> t) & 1)) ? m : 0.0;
+    acc[0] += m * v.x * v.x;
+    acc[1] += m * v.y * v.y;
+    acc[2] += m * v.z * v.z;
+    acc[3] += m * v.x * v.y;
+    acc[4] += m * v.x * v.z;
+    acc[5] += m * v.y * v.z;
+    acc[6] += 0.5 * m * (v.x * v.x + v.y * v.y + v.z * v.z);
+    acc[7] -= mg * (gx * x.x + gy * x.y + gz * x.z);
+  }
+  slots_block_fold<TH_NS>(acc, part);
+}
+
+// stage 2 (one block): thread j folds slot j over the blocks' partials in block order
+static __global__ void k_slots_final(int nblocks, int ns, double scale,
+                                     const double *__restrict__ part, double *__restrict__ out) {
+  const int j = threadIdx.x;
+  if (j >= ns) return;
+  double p = 0.0;
+  for (int b = 0; b < nblocks; b++) p += part[(size_t)b * ns + j];
+  out[j] = scale * p;
+}
+
 // ---- fix setforce / fix addforce ------------------------------------------------------------
 struct ForceFixArgs {
   int nfix;

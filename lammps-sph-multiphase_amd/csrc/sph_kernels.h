@@ -271,7 +271,12 @@ __device__ __forceinline__ bool ghost_keep(const double4 &xi, const double4 &xj)
   return true;
 }
 
-template <int G, int DIM, int VISC, int MODE, bool NT1>
+// VIR (the engine's pair virial, FULL lists only): `virial` is then a scratch array of six
+// doubles per row, and row i stores its own share w_i[ab] = sum_j del_a del_b fpair_ij there
+// (xx yy zz xy xz yz) -- no atomics; k_virial_part / k_slots_final fold the rows and halve the
+// sum, which counts each pair once (virial_fdotr_compute, pair.cpp:1403-1420; sph/idealgas'
+// doubled ev_tally does not reach the virial under vflag_fdotr, so GAS has no factor 2 here).
+template <int G, int DIM, int VISC, int MODE, bool NT1, bool VIR = false>
 __global__ void __launch_bounds__(256)
 k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
         const int *__restrict__ off, const int *__restrict__ nbr,
@@ -284,6 +289,7 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
   constexpr bool TAIT = (MODE & (M_TAIT | M_GAS)) != 0;  // (the force / drho / de body)
   constexpr bool HEAT = (MODE & M_HEAT) != 0;
   constexpr bool HALF = (MODE & M_HALF) != 0;
+  static_assert(!VIR || (TAIT && !HALF), "VIR: a force body over a full list");
   constexpr int U = UNROLL;
   __shared__ TaitPair s_t[(TAIT && !NT1) ? NT2 : 1];
   __shared__ HeatPair s_h[(HEAT && !NT1) ? NT2 : 1];
@@ -397,16 +403,20 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
           jdrho = c.mi * dvdr * wfd;
           jdE = deltaE;
         }
-        if (virial) {
+        if (VIR || virial) {
           const double s = (!HALF || newton || j < nlocal) ? 1.0 : 0.5;
           // (GAS: two ev_tally calls per pair, pair_sph_idealgas.cpp:164-169)
-          const double sf = (GAS ? 2.0 : 1.0) * (HALF ? s * fpair : 0.5 * fpair);
-          v0 += sf * dx * dx;
-          v1 += sf * dy * dy;
-          v2 += sf * dz * dz;
-          v3 += sf * dx * dy;
-          v4 += sf * dx * dz;
-          v5 += sf * dy * dz;
+          double sf = VIR ? fpair : (GAS ? 2.0 : 1.0) * (HALF ? s * fpair : 0.5 * fpair);
+          double qx = dx, qy = dy, qz = dz;
+          // VIR: opaque copies, so that the tally takes no part in how the compiler contracts
+          // the force's own products into FMAs -- a due step leaves the bits a plain step leaves
+          if (VIR) asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz), "+v"(sf));
+          v0 += sf * qx * qx;
+          v1 += sf * qy * qy;
+          v2 += sf * qz * qz;
+          v3 += sf * qx * qy;
+          v4 += sf * qx * qz;
+          v5 += sf * qy * qz;
         }
       }
       if (HEAT && hit_h) {
@@ -436,7 +446,7 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
     fy = group_sum<G>(fy);
     fz = group_sum<G>(fz);
     drho = group_sum<G>(drho);
-    if (virial) {
+    if (VIR || virial) {
       v0 = group_sum<G>(v0);
       v1 = group_sum<G>(v1);
       v2 = group_sum<G>(v2);
@@ -480,7 +490,15 @@ k_force(int inum, int nlocal, int newton, const int *__restrict__ ilist,
       }
       de[i] = accum ? de[i] + dE : dE;
     }
-    if (TAIT && virial) {
+    if (VIR) {
+      double *const w = virial + (size_t)row * 6;
+      w[0] = v0;
+      w[1] = v1;
+      w[2] = v2;
+      w[3] = v3;
+      w[4] = v4;
+      w[5] = v5;
+    } else if (TAIT && virial) {
       atomicAdd(&virial[0], v0);
       atomicAdd(&virial[1], v1);
       atomicAdd(&virial[2], v2);

@@ -38,6 +38,7 @@
 
 #include "sph_kernels.h"
 #include "sph_select.h"
+#include "sph_util.h"
 
 namespace sph {
 
@@ -259,7 +260,18 @@ k_row2_rhosum(int n, int nall, int ntot, const int *__restrict__ off, int stride
   }
 }
 
-template <int G, int U, int VISC, int MODE, bool NT1, bool LP, bool IV, int EXP>
+// VIR (the engine's due steps): the pass also tallies the row's share of the pair virial,
+// w_i[ab] = sum_j del_a del_b fpair_ij with the fpair of the row's force (a masked slot's is
+// 0), and the row's leader lane stores it to vir.w[6 row ..] (xx yy zz xy xz yz); the plain
+// instantiation takes an empty RowVir and is the kernel it was.
+template <bool VIR>
+struct RowVir {};
+template <>
+struct RowVir<true> {
+  double *w;  // six doubles per owned row
+};
+
+template <int G, int U, int VISC, int MODE, bool NT1, bool LP, bool IV, int EXP, bool VIR = false>
 __global__ void __launch_bounds__(256)
 k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
              const int *__restrict__ rcnt,
@@ -267,7 +279,8 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
              const double4 *__restrict__ vr, const int *__restrict__ ty,
              const double *__restrict__ en, const Coefs *__restrict__ cf,
              double4 *__restrict__ fo, double *__restrict__ de, double gx, double gy,
-             double gz, const int *__restrict__ rows, int tbits) {
+             double gz, const int *__restrict__ rows, int tbits, RowVir<VIR> vir) {
+  static_assert(!VIR || ((MODE & (M_TAIT | M_GAS)) != 0 && EXP == 0), "VIR: a force body");
   // GAS (sph/idealgas): the Monaghan body with xf.w = 0.4 e/m/rho (k_eos_gas) and the pair's
   // c_i + c_j, c = sqrt(e * 0.4/m), in the viscosity term; e_j gathered as the heat term's
   constexpr bool GAS = (MODE & M_GAS) != 0;
@@ -315,6 +328,19 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
   const int beg = stride > 0 ? rr * stride : off[rr];
   const int end = live ? (stride > 0 ? beg + rcnt[rr] : off[rr + 1]) : beg;
   double fx = 0.0, fy = 0.0, fz = 0.0, drho = 0.0, dE = 0.0;
+  double wv[6] = {};  // (the virial variant's; dead code otherwise)
+  auto tally = [&](double dx, double dy, double dz, double fpair) {
+    // opaque copies: the tally must not take part in how the compiler contracts the force's
+    // own products into FMAs (the Morris variant otherwise differed from the plain kernel in
+    // the last bit of f), so that a due step leaves the fields a plain step leaves
+    asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz), "+v"(fpair));
+    wv[0] += dx * dx * fpair;
+    wv[1] += dy * dy * fpair;
+    wv[2] += dz * dz * fpair;
+    wv[3] += dx * dy * fpair;
+    wv[4] += dx * dz * fpair;
+    wv[5] += dy * dz * fpair;
+  };
   int jn[U];
   chunk_idx<G, U, IV>(rn, beg, lane, jn);
   for (int k0 = beg; LP ? __any(chunk_pos<G, U, IV>(k0, lane, 0) < end)
@@ -378,6 +404,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
           fy += dy * fpair;
           fz += dz * fpair;
           dE += -0.5 * fpair * dvdr;
+          if constexpr (VIR) tally(dx, dy, dz, fpair);
         } else {
           double fvisc = c.viscC * rcp1(vi.w * vj[u].w);
           fvisc = hit ? fvisc * ((-c.mm) * wfd) : 0.0;
@@ -386,6 +413,7 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
           fy += dy * fpair + vely * fvisc;
           fz += dz * fpair + velz * fvisc;
           dE += -0.5 * (fpair * dvdr + fvisc * (velx * velx + vely * vely + velz * velz));
+          if constexpr (VIR) tally(dx, dy, dz, fpair);
         }
         drho += c.mj * dvdr * wfd;
       }
@@ -415,6 +443,14 @@ k_row2_force(int n, int nall, int ntot, const int *__restrict__ off, int stride,
       fo[row] = make_double4(fx + m * gx, fy + m * gy, fz + m * gz, drho);
     }
     de[row] = dE;
+  }
+  if constexpr (VIR) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) wv[k] = group_sum<G>(wv[k]);
+    if (lane == 0 && live) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) vir.w[(size_t)row * 6 + k] = wv[k];
+    }
   }
 }
 
@@ -488,8 +524,12 @@ inline void row2_rhosum(bool nt1, hipStream_t s, const Row2Args &b) {
   });
 }
 
-inline void row2_force(bool nt1, int visc, int mode, hipStream_t s, const Row2Args &b) {
-  const int exp1 = nt1 ? b.exp : 0;  // the study variants are for one type
+// vw != nullptr: the virial variant (RowVir; the modes with a force body)
+inline void row2_force(bool nt1, int visc, int mode, hipStream_t s, const Row2Args &b,
+                       double *vw = nullptr) {
+  SPH_REQUIRE(!vw || (mode & (M_TAIT | M_GAS)), SPH_HIP_EINVAL,
+              "row2_force: no virial variant of force mode %d", mode);
+  const int exp1 = (nt1 && !vw) ? b.exp : 0;  // the study variants are for one type
   row2_select(nt1, b, [&](auto tile, auto lp, auto iv, auto t) {
     constexpr int G = tile.v[0], U = tile.v[1];
     constexpr bool LP = lp, IV = iv, NT1 = t;
@@ -503,10 +543,15 @@ inline void row2_force(bool nt1, int visc, int mode, hipStream_t s, const Row2Ar
           const RowArgs &a = b.a;
           const int grid = (int)(((long long)a.n * G + 255) / 256);
           if (grid == 0) return;
-          hipLaunchKernelGGL((k_row2_force<G, U, VISC, MODE, NT1, LP, IV, EXP>), dim3(grid),
-                             dim3(256), 0, s, a.n, b.nall, b.ntot, a.off, b.stride, b.rcnt, a.nbr,
-                             a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy, a.gz, b.rows,
-                             b.tbits ? 1 : 0);
+          select_bool(vw != nullptr, [&](auto vi) {
+            constexpr bool VIR = vi && (MODE & (M_TAIT | M_GAS)) != 0 && EXP == 0;
+            RowVir<VIR> vir{};
+            if constexpr (VIR) vir.w = vw;
+            hipLaunchKernelGGL((k_row2_force<G, U, VISC, MODE, NT1, LP, IV, EXP, VIR>),
+                               dim3(grid), dim3(256), 0, s, a.n, b.nall, b.ntot, a.off, b.stride,
+                               b.rcnt, a.nbr, a.xf, a.vr, a.ty, a.en, a.cf, a.fo, a.de, a.gx, a.gy,
+                               a.gz, b.rows, b.tbits ? 1 : 0, vir);
+          });
         };
         // (EXP: outputs meaningless, study builds only, make STUDY=1; Monaghan, M_TAIT)
         if constexpr (STUDY_BUILD && VISC == SPH_VISC_MONAGHAN && MODE == M_TAIT)
