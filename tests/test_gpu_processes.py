@@ -81,10 +81,12 @@ def merge(snaps, step, n):
     return out
 
 
-@pytest.mark.parametrize("mode,pg", [(0, (2, 1, 1)), (1, (2, 1, 1)), (0, (1, 2, 2))])
+@pytest.mark.parametrize("mode,pg", [(0, (2, 1, 1)), (1, (2, 1, 1)), (0, (1, 2, 2)),
+                                     (0, (3, 1, 1)), (1, (3, 1, 1))])
 def test_processes_c2_rebuilds_migration(gpu, tmp_path, mode, pg):
     """C2 from rest, 40 steps, rebuilds + migrations every 5 (the brick face at x = 6 is
-    crossed), as separate processes; counts bit-exact and fields 1e-10 vs the one-process
+    crossed; on 3x1x1, three ranks with distinct lower and upper neighbours, the faces at
+    x = 0, 4 and 8 in both directions), as separate processes; counts bit-exact and fields 1e-10 vs the one-process
     oracle at every snapshot."""
     nsteps = [5, 25, 40]
     P = int(np.prod(pg))
@@ -109,9 +111,10 @@ def test_processes_c2_rebuilds_migration(gpu, tmp_path, mode, pg):
 @pytest.mark.parametrize("mode,pg,dim,nx,drift", [(0, (2, 1, 1), 3, 8, 0), (1, (2, 1, 1), 3, 8, 0),
                                                   (0, (2, 2, 1), 2, 12, 0),
                                                   (0, (2, 1, 1), 3, 10, 200.0),
-                                                  (1, (2, 2, 1), 2, 16, 200.0)])
+                                                  (1, (2, 2, 1), 2, 16, 200.0),
+                                                  (0, (3, 1, 1), 3, 12, 200.0)])
 def test_processes_c5_phase_change(gpu, tmp_path, mode, pg, dim, nx, drift):
-    """C5 (bubble_growth stack + fix phase_change, rebuild every step) on 2 or 4 processes for
+    """C5 (bubble_growth stack + fix phase_change, rebuild every step) on 2 to 4 processes for
     5 steps against pyoracle.MpRefRun(procgrid): per-rank RanPark streams, dmass reverse comm,
     the nins allgather and rank-by-rank tag_extend all cross process boundaries.  drift: atoms
     migrate every step and Atom::sort runs every 2 steps, so every rank's candidates meet the

@@ -181,3 +181,121 @@ def test_phase_change_meets_candidates_in_local_order():
     # every view lists its owned atoms in the tracked local order
     bv = a1.bviews[0]
     assert np.array_equal(bv.gid[:bv.nlocal], a1.local[0])
+
+
+# ---- three bricks along a dimension: distinct lower and upper neighbours ----------------
+def test_exchange_bricks_three_ranks_upper_buffer_first():
+    """CommBrick::exchange on 3x1x1 by hand (comm_brick.cpp:634-672): six atoms, two per
+    rank; 1 leaves rank 0 downwards across the periodic face, 2 and 3 leave rank 1 to either
+    side, 4 leaves rank 2 upwards across the periodic face.  Every rank sends its leavers to
+    both neighbours and appends what falls into its slab, the upper neighbour's buffer first:
+    rank 0 gets 2 (from its upper neighbour 1) before 4 (from its lower neighbour 2), rank 2
+    gets 1 (from its upper neighbour 0) before 3 (from its lower neighbour 1)."""
+    x = np.zeros((6, 3))
+    x[:, 0] = [0.5, 2.5, 0.2, 2.2, 0.7, 2.6]
+    x[:, 1:] = 0.5
+    one = np.ones(6)
+    s = po.System(3, np.zeros(3), np.array([3.0, 1.0, 1.0]), (1, 1, 1), x, np.zeros((6, 3)),
+                  np.ones(6, dtype=np.int32), one.copy(), one.copy(), one.copy(), 1,
+                  np.array([0.0, 1.0]))
+    pg = (3, 1, 1)
+    grid = po.brick_grid(s, pg)
+    assert [g["neigh"][0].tolist() for g in grid] == [[2, 1], [0, 2], [1, 0]]   # [lower, upper]
+    new = po.exchange_bricks(s, pg, [[0, 1], [2, 3], [4, 5]])
+    assert [l.tolist() for l in new] == [[0, 2, 4], [], [5, 1, 3]]
+    # every atom ends on the rank whose slab holds it, exactly once
+    own = po.brick_owner(s, x, pg)
+    for r, l in enumerate(new):
+        assert np.all(own[l] == r)
+    # a rank whose leavers hole-fill: [6 atoms] 0 and 2 leave -> slot 0 takes the last atom
+    x2 = np.zeros((6, 3))
+    x2[:, 0] = [2.9, 1.5, 0.1, 1.2, 1.7, 1.4]
+    s2 = s.copy()
+    s2.x = x2
+    new = po.exchange_bricks(s2, pg, [[], [0, 1, 2, 3, 4, 5], []])
+    assert [l.tolist() for l in new] == [[2], [5, 1, 4, 3], [0]]
+
+
+@pytest.mark.parametrize("pg", [(3, 1, 1), (1, 3, 1), (3, 3, 1)])
+def test_three_brick_views_hold_the_single_process_ghosts(pg):
+    """borders_bricks on a 3-grid against po.borders: a rank's ghosts are exactly the single
+    process' atoms and periodic images (atom, image) that lie within the ghost cut of its
+    sub-box along the split dimensions, its own atoms left out -- as a multiset per rank.
+    The interior brick shifts nothing; the edge bricks' images carry -1 / +1."""
+    s = bubble_system(12, slab=True)
+    cut = 0.3
+    g = po.borders(s, cut)
+    gid = np.concatenate([np.arange(s.n), g.owner])
+    img = np.concatenate([np.zeros((s.n, 3), dtype=np.int64), g.image.astype(np.int64)])
+    views = po.borders_bricks(s, cut, pg)
+    assert sum(v.nlocal for v in views) == s.n
+    prd = s.boxhi - s.boxlo
+    for v in views:
+        inside = np.ones(g.nall, dtype=bool)
+        for d in range(3):
+            if pg[d] > 1:
+                inside &= (g.x[:, d] >= v.lo[d] - cut) & (g.x[:, d] <= v.hi[d] + cut)
+        mine = np.zeros(g.nall, dtype=bool)
+        mine[v.gid[:v.nlocal]] = True          # (owned atoms come first in g, image 0)
+        want = sorted(map(tuple, np.column_stack([gid, img])[inside & ~mine].tolist()))
+        nl = v.nlocal
+        got = sorted(map(tuple, np.column_stack([v.gid[nl:], v.image[nl:]]).tolist()))
+        assert got == want, v.rank
+        assert np.allclose(v.x, s.x[v.gid] + v.image * prd, atol=1e-14, rtol=0)
+        for d in range(3):
+            if pg[d] == 3 and v.loc[d] == 1:   # interior: no image along d
+                assert not v.image[:, d].any()
+            if pg[d] == 3 and v.loc[d] == 0:
+                assert v.image[:, d].min() == -1 and v.image[:, d].max() == 0
+        for k in range(v.nghost):              # the sender's copy of each ghost is the same atom
+            assert views[v.src_rank[k]].gid[v.src_idx[k]] == v.gid[nl + k]
+
+
+def test_counterflow_depends_on_arrival_order(monkeypatch):
+    """The premise of tests/test_c5_bricks3.py::test_c5_bricks3_migration_local_order, from
+    the oracle alone: every rank of 3x1x1 receives atoms from both neighbours in the first
+    exchange, and appending the lower neighbour's buffer before the upper one's makes fix
+    phase_change create other atoms -- so an engine that mixed the two up would fail there."""
+    from test_c5_bricks3 import arrivals_by_side, counterflow_case
+    pg = (3, 1, 1)
+    s, ph = counterflow_case(0)
+    real = po.exchange_bricks
+
+    def lower_first(sysm, pg_, local, x=None):
+        was = {int(i): r for r, l in enumerate(local) for i in l}
+        out = []
+        for r, l in enumerate(real(sysm, pg_, local, x)):
+            grid = po.brick_grid(sysm, pg_)[r]["neigh"][0]
+            src = np.array([was[int(i)] for i in l], dtype=np.int64)
+            out.append(np.concatenate([l[src == r], l[(src == grid[0]) & (src != r)],
+                                       l[(src == grid[1]) & (src != r)]]))
+        return out
+
+    runs = []
+    for swap in (False, True):
+        if swap:
+            monkeypatch.setattr(po, "exchange_bricks", lower_first)
+        ref = po.MpRefRun(s, ph, procgrid=pg)
+        ref.setup()
+        before = [l.copy() for l in ref.local]
+        ref.run(1)
+        arr = arrivals_by_side(ref, before, pg)
+        assert all(lo >= 10 and up >= 10 for lo, up in arr), arr
+        ref.run(3)
+        runs.append(ref)
+    a, b = runs
+    assert a.ninserted >= 2 and b.ninserted >= 2
+    n0 = s.n
+    assert not (a.ninserted == b.ninserted and
+                np.allclose(a.s.x[n0:], b.s.x[n0:], rtol=0, atol=1e-9))
+
+
+def test_three_brick_migration_premises():
+    """The premise of tests/test_gpu_bricks3.py::test_bricks3_migration_both_directions, from
+    the single-process reference alone: over the 40 steps atoms change their brick along x
+    upwards and downwards, and across the periodic face between brick 0 and brick 2."""
+    from test_gpu_bricks3 import migration_case
+    s, ph, ref, b0, b1 = migration_case()
+    d = (b1 - b0) % 3
+    assert (d == 1).sum() >= 1 and (d == 2).sum() >= 1
+    assert (((b0 == 0) & (b1 == 2)) | ((b0 == 2) & (b1 == 0))).sum() >= 1
